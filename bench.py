@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MSCKF measurement-updates/sec on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one complete measurement update (K1..K7: per-feature Jacobian stack,
 nullspace projection, chi-square gate, QR compression, gain, Joseph covariance
@@ -29,6 +29,11 @@ N > 1 : (launched by torch.distributed.run, one rank per GPU; only RANK / LOCAL_
 
 Rank 0 prints ONE JSON line.  The oracle (oracle/msckf_oracle.py) is only timed
 as the CPU baseline; it is never on the measured GPU path.
+
+--dump-outputs DIR: rank 0 writes what the timed path returned on its last timed
+step (status, dx, P_new, accepted; the strong case at N > 1) as DIR/<name>.npy in
+float64.  The batches are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import ctypes as C
@@ -113,6 +118,24 @@ def pmc_executed_flops(kernel_prefixes):
             tot += float(v) * 128.0 * k["calls"]
             calls += k["calls"]
     return (tot / calls, os.path.basename(files[-1])) if calls else None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, status, dx, P_new, accepted):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array of an update's result.  An array that would take the total
+    past DUMP_LIMIT_BYTES is written as a sample of its flattened entries: the same seeded positions for the same shape,
+    so dumps of two builds still compare entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_LIMIT_BYTES - 4096                          # room for the four .npy headers
+    for name, a in (("status", [status]), ("dx", dx), ("accepted", accepted), ("P_new", P_new)):
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > left:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, left // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def blas_threads():
@@ -219,7 +242,10 @@ def main():
     ap.add_argument("--no-extra-configs", action="store_true", help="headline only (profiling runs)")
     ap.add_argument("--no-mode-i-headline", action="store_true", help="skip the one-minute dense-eye CPU baseline at the headline")
     ap.add_argument("--force-dist", action="store_true", help="run the sharded code path even at world size 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the result of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -247,10 +273,13 @@ def main():
             eng.update_problem(probs4[i % 4])
         eng.sync()
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(args.steps - 1):
             eng.update_problem(probs4[i % 4])
+        last = eng.update_problem(probs4[(args.steps - 1) % 4])    # the last timed call: what --dump-outputs writes
         eng.sync()
         call_s = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last.status, last.dx, last.P_new, last.accepted)
     prob, res, one, head, costs = time_config(N, Fg, M, args.steps, args.warmup, device=local_rank, host_reps=20)
     stats = one.stats
     us_step = head["us_per_update"]
@@ -598,7 +627,7 @@ def bench_sharded(args, world, rank, local_rank):
         groups = drv.groups
         drv.close()
         eng.close()
-        return seconds, groups, status, int(acc.sum()), n_rej
+        return seconds, groups, status, int(acc.sum()), n_rej, (dx, P, acc)
 
     # the same 8000-feature update on ONE GPU (rank 0's, unsharded, resident in HBM): what the strong-scaling figure is a
     # speed-up over.  The other ranks wait in the bootstrap of the first sharded case.
@@ -612,9 +641,11 @@ def bench_sharded(args, world, rank, local_rank):
             e1.sync()
             ms1, _ = e1.run_timed(30)
             one_gpu_us = 1e3 * ms1 / 30
-    s_seconds, s_groups, st2, s_acc, s_rej = run_case(8000, args.steps, args.warmup, "_strong")
+    s_seconds, s_groups, st2, s_acc, s_rej, s_out = run_case(8000, args.steps, args.warmup, "_strong")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, st2, *s_out)
     weak_steps = max(10, min(args.steps, 100))
-    seconds, groups, st1, _, _ = run_case(Fg * world, weak_steps, min(args.warmup, 10), "_weak")
+    seconds, groups, st1, _, _, _ = run_case(Fg * world, weak_steps, min(args.warmup, 10), "_weak")
     line = None
     if rank == 0:
         line = {

@@ -72,3 +72,21 @@ def test_one_gpu_line_shape():
     assert "workload" in j["config"] and "model" not in j["config"]
     r = j["roofline"]
     assert 0.0 < r["frac"] < 1.0 and r["achieved"] > 0 and r["peak"] > 0
+
+
+def test_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the result of the LAST timed call: with --steps 3 over the batches of seeds 0..3 in rotation that
+    is seed 2's update, checked against the oracle like every other drop-in call."""
+    import numpy as np
+    from msckf_amd import synth
+    from oracle import msckf_oracle as oracle
+    out = tmp_path / "dump"
+    j = _run_bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-configs", "--dump-outputs", str(out)])
+    assert j["steps"] == 3
+    got = {n: np.load(str(out / (n + ".npy"))) for n in ("status", "dx", "accepted", "P_new")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    ref = oracle.update(synth.make_problem(30, 2000, 10, seed=2), dense_noise=False)
+    assert got["status"].tolist() == [ref["status"]] == [0]
+    assert np.array_equal(got["accepted"], ref["accepted"].astype(np.float64))
+    assert np.linalg.norm(got["dx"] - ref["dx"]) < 1e-8 * np.linalg.norm(ref["dx"])
+    assert np.linalg.norm(got["P_new"] - ref["P_new"]) < 1e-8 * np.linalg.norm(ref["P_new"])

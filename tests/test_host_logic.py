@@ -430,3 +430,30 @@ def test_plan_flags_of_the_header_and_the_binding_agree():
     vals = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (MSCKF_FLAG_\w+) (\d+)", hdr)}
     assert vals["MSCKF_FLAG_TREE_PLAN"] == _ffi.FLAG_TREE_PLAN == 1
     assert vals["MSCKF_FLAG_BAND_ONLY"] == _ffi.FLAG_BAND_ONLY == 2
+
+
+def test_bench_dump_outputs_files_and_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float64 .npy per result array; an array past the size cap is written as a sample of its
+    entries at seeded positions, the same on every call, and the files stay within the cap."""
+    import bench
+    d = 40
+    dx, P, acc = np.arange(d, dtype=np.float64), np.arange(d * d, dtype=np.float64).reshape(d, d), np.array([1, 0, 1], np.uint8)
+    bench.dump_outputs(str(tmp_path / "full"), 0, dx, P, acc)
+    got = {n: np.load(str(tmp_path / "full" / (n + ".npy"))) for n in ("status", "dx", "accepted", "P_new")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["status"].tolist() == [0.0] and np.array_equal(got["dx"], dx) and np.array_equal(got["P_new"], P)
+    assert got["accepted"].tolist() == [1.0, 0.0, 1.0]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 8 * (1 + d + 3 + 100))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), 0, dx, P, acc)
+    a, b = np.load(str(tmp_path / "a" / "P_new.npy")), np.load(str(tmp_path / "b" / "P_new.npy"))
+    assert a.shape == (100,) and np.array_equal(a, b) and np.all(np.diff(a) > 0) and np.isin(a, P).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_bench_rejects_zero_steps():
+    """--steps sets the number of timed calls; zero of them would measure nothing and is refused before any device work."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -5,7 +5,7 @@ import os, subprocess, sys
 name = sys.argv[1]
 code = r'''
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, sys.argv[1])
 import numpy as np, msckf_amd
 from msckf_amd import synth
 from msckf_amd.api import UpdateEngine
@@ -22,5 +22,5 @@ print("%.1f" % best)
 for trial in range(3):
     for val in ("1", "0"):
         env = dict(os.environ); env[name] = val
-        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, "-c", code, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))], env=env, capture_output=True, text=True)
         print(f"{name}={val}: {out.stdout.strip()} us per call (best of 5 x 200)", flush=True)

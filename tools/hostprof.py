@@ -2,7 +2,7 @@
 """Host-side phases of the drop-in call (MSCKF_HOSTPROF=1 prints them when the engine closes): rotating batches at (N, F, M)."""
 import os, sys, time
 os.environ["MSCKF_HOSTPROF"] = "1"
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, msckf_amd
 from msckf_amd import synth
 from msckf_amd.api import UpdateEngine

@@ -5,7 +5,8 @@ tag=${1:-it}
 kexpr=${2:-"golden or band or ring or ragged or sweep or headline or shipped"}
 out=gpurun_out/r3
 mkdir -p $out
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_f32.py -x -q -k "$kexpr" > $out/${tag}_tests.log 2>&1
 rc=$?
 tail -3 $out/${tag}_tests.log

@@ -1,7 +1,8 @@
 #!/bin/bash
 # usage (on the GPU box): tools/ktimeline.sh N F M [dtype]  -> start / end of every kernel of the LAST resident update of one
 # config, relative to its first kernel (rocprofv3 --kernel-trace): shows what runs beside what (root sweep | k_gain_stream)
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 out=gpurun_out/tl_$1_$2_$3
 rm -rf $out; mkdir -p $out
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out -- python3 tools/one_config.py $1 $2 $3 3 $4 > $out.log 2>&1

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): tools/ktimeline2.sh u15|u30|frame|mixed -> kernel timeline of the last resident update of that batch
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 out=gpurun_out/tl2_$1
 rm -rf $out; mkdir -p $out
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out -- python3 tools/ktimeline_prob.py $1 > $out.log 2>&1

@@ -9,8 +9,9 @@ tag=${1:-r04}
 shift
 out=gpurun_out/profiles_$tag
 mkdir -p $out
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-cd $GRAFT_REPO_ROOT
+cd "$ROOT"
 if [ $# -ge 3 ]; then
   CMD="python3 tools/one_config.py $*"
 else

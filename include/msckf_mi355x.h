@@ -291,8 +291,26 @@ int msckf_set_exchange_span(msckf_ctx* ctx, int32_t max_span);
  * NB (changed in round 3, same ABI version): the value is the sweep mode + 1, not a boolean -- test `> 0`, never
  * `== 1` (a caller that did fell back to root blocks for the two ring modes). */
 int msckf_band_rule(const msckf_ctx* ctx, int32_t N, int32_t max_span);
-size_t msckf_group_record_doubles(const msckf_ctx* ctx);   /* N + 1 + gate-byte doubles (msckf_set_exchange_mask) + N * 3660 (8190 with 90-column slots) */
+size_t msckf_group_record_doubles(const msckf_ctx* ctx);   /* N + 1 + gate-byte doubles (msckf_set_exchange_mask) + N * 3660 (8190 with 90-column slots)
+                                                            + 1 + rows x (6N + 1) with msckf_set_exchange_split */
 int msckf_export_groups(msckf_ctx* ctx, void* dst, int device_ptr, int32_t* n_accepted /* nullable */);
+
+/* Split records: long tracks (more than 10 clone slots) split under the group exchange as on one GPU.
+ * msckf_exchange_split_rule evaluates the WHOLE batch (every rank passes the same arguments and gets the same answer,
+ * no collective): out[0] 1 when the batch is exchanged as split records, out[1] the band span after the split (what
+ * msckf_set_exchange_span must be told; the longest track when not split), out[2] the remainder rows one record holds
+ * (the largest shard's sum of 3 per view group of its long tracks, rounded up to 16), out[3] the whole batch's bound
+ * on them.  `flags` (nullable, n_shards x N bytes) receives the first-slot groups of every shard's record (narrow
+ * blocks start at their view group's first slot) for msckf_run_merge_groups_flags.  ctx may be null (defaults).
+ * Not split: a long track with views out of slot order, more than 31 views or more than 6 groups, a batch mostly of
+ * 11 - 15-slot tracks, more remainder rows than K6-K7 takes as they are. */
+int msckf_exchange_split_rule(const msckf_ctx* ctx, int32_t N, int32_t F, const int32_t* view_ptr, const int32_t* obs_slot,
+                              int32_t n_shards, const int32_t* bounds /* [n_shards + 1] */, int32_t out[4], uint8_t* flags);
+/* Record capacity for split records (out[2] and out[3] of the rule; 0 = off, today's records): msckf_set_features splits
+ * long tracks with the group exchange on, the record grows by a remainder section [count word | rows x (6N + 1)]
+ * (msckf_group_record_doubles), rank 0's merge takes those rows as K6-K7's second source.  Same values on every rank;
+ * call before msckf_set_features. */
+int msckf_set_exchange_split(msckf_ctx* ctx, int32_t rows_per_record, int32_t rows_total);
 int msckf_run_merge_groups(msckf_ctx* ctx, const void* records, int32_t n_records, int device_ptr,
                            int32_t total_accepted /* < 0: the sum of the counts in the records */);
 

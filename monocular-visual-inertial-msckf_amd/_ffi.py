@@ -33,7 +33,7 @@ SYMBOLS = [
     "msckf_comm_unique_id", "msckf_comm_init", "msckf_comm_destroy", "msckf_comm_gather", "msckf_comm_broadcast",
     "msckf_comm_allreduce", "msckf_comm_buffer", "msckf_comm_put", "msckf_comm_get",
     "msckf_set_exchange_mask", "msckf_result_range_doubles", "msckf_get_shared_result", "msckf_set_exchange_span",
-    "msckf_debug_split", "msckf_debug_set_rem_direct_rows",
+    "msckf_debug_split", "msckf_debug_set_rem_direct_rows", "msckf_exchange_split_rule", "msckf_set_exchange_split",
 ]
 
 
@@ -147,6 +147,10 @@ def load():
     lib.msckf_comm_get.restype = C.c_int
     lib.msckf_set_exchange_span.argtypes = [vp, C.c_int32]
     lib.msckf_set_exchange_span.restype = C.c_int
+    lib.msckf_exchange_split_rule.argtypes = [vp, C.c_int32, C.c_int32, _ip, _ip, C.c_int32, _ip, _ip, vp]
+    lib.msckf_exchange_split_rule.restype = C.c_int
+    lib.msckf_set_exchange_split.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.msckf_set_exchange_split.restype = C.c_int
     lib.msckf_set_exchange_mask.argtypes = [vp, C.c_int32, _ip]
     lib.msckf_set_exchange_mask.restype = C.c_int
     lib.msckf_result_range_doubles.argtypes = [vp]

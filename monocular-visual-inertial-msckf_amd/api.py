@@ -68,6 +68,21 @@ class Selection:
         return (self.flags & _ffi.SEL_REFRESHED) > 0
 
 
+def exchange_split_rule(prob: UpdateProblem, shards, lib=None, handle=None) -> dict:
+    """`UpdateEngine.exchange_split_rule` without an engine (the library's defaults; no GPU needed)."""
+    lib = lib if lib is not None else _ffi.load()
+    vp = np.ascontiguousarray(prob.view_ptr, dtype=np.int32)
+    slots = np.ascontiguousarray(np.asarray(prob.obs_slot).reshape(-1), dtype=np.int32)
+    bounds = np.ascontiguousarray([s[0] for s in shards] + [shards[-1][1]], dtype=np.int32)
+    out = np.zeros(4, dtype=np.int32)
+    flags = np.zeros((len(shards), int(prob.N)), dtype=np.uint8)
+    rc = lib.msckf_exchange_split_rule(handle, int(prob.N), int(prob.F), _ffi.iptr(vp), _ffi.iptr(slots), len(shards),
+                                       _ffi.iptr(bounds), _ffi.iptr(out), flags.ctypes.data)
+    if rc != 0:
+        raise _ffi.EngineError(rc, "msckf_exchange_split_rule")
+    return {"split": bool(out[0]), "span": int(out[1]), "rows": int(out[2]), "total": int(out[3]), "flags": flags}
+
+
 class UpdateEngine:
     """One context on one MI355X.  Not thread-safe (one engine per host thread)."""
 
@@ -409,6 +424,18 @@ class UpdateEngine:
         then lays its group record out for the sweep mode of the whole batch (also the ring-buffered modes, N > 37
         or tracks of 11 - 15 slots).  0 = not told (60-column k_sweep form only)."""
         self._check(self._lib.msckf_set_exchange_span(self._h, int(max_span)), allow_noop=False)
+
+    def exchange_split_rule(self, prob: UpdateProblem, shards) -> dict:
+        """Split records for the WHOLE batch `prob` cut into `shards` ([lo, hi) per rank) -- the same answer on every rank
+        (`msckf_exchange_split_rule`): `split`, the band `span` after the split (for `set_exchange_span`), the remainder
+        `rows` one record holds and their `total` bound (for `set_exchange_split`), the (world, N) uint8 group `flags` of
+        every shard's record (for `merge_groups_flags`)."""
+        return exchange_split_rule(prob, shards, self._lib, self._h)
+
+    def set_exchange_split(self, rows: int, total: int = 0):
+        """Record capacity for split records (the rule's `rows` / `total`; 0 = off: long tracks keep root blocks).  Same value
+        on every rank, before `load`."""
+        self._check(self._lib.msckf_set_exchange_split(self._h, int(rows), int(total)), allow_noop=False)
 
     def group_record_doubles(self) -> int:
         return int(self._lib.msckf_group_record_doubles(self._h))

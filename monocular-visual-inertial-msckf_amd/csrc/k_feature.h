@@ -1263,4 +1263,49 @@ __global__ __launch_bounds__(256) void k_rem_scatter(RemScatterArgs p) {
     }
 }
 
+// Merging rank of a sharded update with split records (msckf_set_exchange_split): the remainder rows every record carries behind
+// its triangle slots (k_rem_scatter laid them down there, count word in front) into ONE dense row-major matrix [rows][6N + 1] for
+// K6-K7's second source, in record order, zero rows up to the next multiple of 16, the row count where K6-K7 reads it at the head
+// of its launch.  Workgroup r copies record r (its first row: the rows of the records in front of it, summed by the workgroup
+// itself), workgroup n_rec pads and publishes.  Nothing goes through the host.
+struct RemCollectArgs {
+    const double* recs; long long rec_stride;    // the gathered records, rec_stride doubles apart
+    long long rem_off;                           // a record's count word (int [0] row blocks, [1] rows), doubles from its head
+    int rec_rows;                                // rows a record's section holds
+    int n_rec;
+    int ld;                                      // 6N + 1
+    int max_rows;                                // rows `out` holds (a multiple of 16)
+    double* out;
+    int* nrows;                                  // [0] row blocks of 16, [1] rows
+    int* status;                                 // the result range's status words: bit 1 of word 4 when the records hold more than max_rows
+};
+__device__ __forceinline__ int rem_record_rows(const RemCollectArgs& p, int r) {
+    const int n = reinterpret_cast<const int*>(p.recs + (size_t)r * p.rec_stride + p.rem_off)[1];
+    return n < 0 ? 0 : (n > p.rec_rows ? p.rec_rows : n);
+}
+__global__ __launch_bounds__(256) void k_rem_collect(RemCollectArgs p) {
+    __shared__ int s_red[256];
+    const int t = threadIdx.x, me = (int)blockIdx.x;
+    int part = 0;
+    for (int i = t; i < min(me, p.n_rec); i += 256) part += rem_record_rows(p, i);
+    s_red[t] = part;
+    __syncthreads();
+    for (int k = 128; k >= 1; k >>= 1) { if (t < k) s_red[t] += s_red[t + k]; __syncthreads(); }
+    const int row0 = s_red[0];
+    if (me == p.n_rec) {                              // row0 = all rows
+        const int rows = min(row0, p.max_rows);
+        const int pad = ((rows + 15) & ~15) - rows;
+        for (int e = t; e < pad * p.ld; e += 256) p.out[(size_t)rows * p.ld + e] = 0.0;
+        if (t == 0) {
+            p.nrows[0] = (rows + 15) >> 4; p.nrows[1] = rows;
+            if (row0 > p.max_rows) p.status[4] |= 2;
+        }
+        return;
+    }
+    const int q = min(rem_record_rows(p, me), max(p.max_rows - row0, 0));
+    const double* src = p.recs + (size_t)me * p.rec_stride + p.rem_off + 1;
+    double* dst = p.out + (size_t)row0 * p.ld;
+    for (int e = t; e < q * p.ld; e += 256) dst[e] = src[e];
+}
+
 }  // namespace msckf

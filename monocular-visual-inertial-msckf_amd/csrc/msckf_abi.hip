@@ -304,6 +304,14 @@ struct msckf_ctx {
     bool xchg = false;                    // requested by msckf_set_group_exchange
     int xchg_span = 0;                    // longest track of the WHOLE batch in clone slots (msckf_set_exchange_span); 0: not told
     bool xchg_planned = false;            // the current plan has the record layout
+    // split records (msckf_set_exchange_split): long tracks are split under the group exchange too; behind its triangle slots a
+    // record carries a remainder section [count word | xsplit_rows rows of 6N + 1 doubles] (the rows of its accepted long tracks)
+    int xsplit_rows = 0;                  // rows one record's remainder section holds (0: off, records as before)
+    int xsplit_total = 0;                 // bound on the remainder rows of the whole batch (the merge's second source of rows)
+    bool x_rem_merge = false;             // the merge being launched carries split records: K6-K7 has TWO sources of rows
+    int x_rem_blocks = 0;                 // ... row blocks of 16 the merge's dense rows may fill (dRem)
+    bool x_rem_last = false;              // the last run was such a merge (status word 4 is its)
+    bool x_status1 = false;               // status word 1 was written by a launch of the last merge (its early update)
     std::vector<double> h_xflags;         // [N] 1.0 where this shard has tracks starting at the slot
     std::vector<double> x_key;            // flags of the last merged records (plan cache of msckf_run_merge_groups)
     int x_nrec = 0;
@@ -542,6 +550,9 @@ void seat_result_views(msckf_ctx* c) {
 
 // doubles in front of the group triangles of an export record: N flags | accepted count | gate bytes
 inline size_t rec_head(const msckf_ctx* c) { return (size_t)c->N + 1 + (size_t)c->xmask_doubles; }
+// split records: the remainder section behind the triangle slots -- a count word (int [0] row blocks of 16, [1] rows, as
+// k_rem_scatter publishes them) and xsplit_rows rows of 6N + 1 doubles
+inline size_t rec_rem_doubles(const msckf_ctx* c) { return c->xsplit_rows > 0 ? 1 + (size_t)c->xsplit_rows * (6 * (size_t)c->N + 1) : 0; }
 int sweep_mode_for(const msckf_ctx* c, int N, int max_span);
 // sweep mode of the group exchange at N clones: that of the whole batch's longest track when the caller told it
 // (every rank then lays its record out alike), else the 60-column k_sweep form only (-1: no group exchange)
@@ -550,6 +561,7 @@ inline int xchg_mode(const msckf_ctx* c, int N) {
     return sweep_mode_for(c, N, 1) == 0 ? 0 : -1;
 }
 inline size_t rec_slot(const msckf_ctx* c) { const int m = xchg_mode(c, c->N); return xchg_slot(m < 0 ? 0 : m); }
+inline size_t rec_rem_off(const msckf_ctx* c) { return rec_head(c) + (size_t)c->N * rec_slot(c); }
 
 // the clone set changed: feature batch, plan and results of the old layout are void
 void invalidate_batch(msckf_ctx* c) {
@@ -562,8 +574,8 @@ void invalidate_batch(msckf_ctx* c) {
 
 // Tracks that span more than WIDE_SPAN clone slots are SPLIT (k_feature.h: two-level nullspace basis) wherever a batch is
 // planned for this context alone: their narrow blocks are ordinary tracks of the 60-column band pipeline, their remainder
-// blocks a small dense QR beside it.  Any window size, both dtypes.  Not with the group exchange of a sharded update (its
-// record layout is the band pipeline's; such a batch keeps one plan for every track) nor where a plan is forced.
+// blocks a small dense QR beside it.  Any window size, both dtypes.  Under the group exchange of a sharded update only with
+// split records (msckf_set_exchange_split: the remainder rows ride in the record); never where a plan is forced.
 constexpr int WIDE_SPAN = SPLIT_GSLOTS;
 // the sequential block update (k_gstream.h) on DENSE rows at this window size: strips and LDS
 bool gstream_ok_dc(const msckf_ctx* c, int dc) {
@@ -572,7 +584,7 @@ bool gstream_ok_dc(const msckf_ctx* c, int dc) {
     return ns <= GS_MAX_NS && gstream_lds_doubles(ns, nb) * 8 <= (size_t)(LDS_MAX_BYTES - 1024);
 }
 bool split_ok(const msckf_ctx* c, int N) {
-    if ((c->cfg.flags & (MSCKF_FLAG_TREE_PLAN | MSCKF_FLAG_BAND_ONLY)) || c->xchg) return false;
+    if ((c->cfg.flags & (MSCKF_FLAG_TREE_PLAN | MSCKF_FLAG_BAND_ONLY)) || (c->xchg && c->xsplit_rows == 0)) return false;
     static const bool off = [] { const char* e = std::getenv("MSCKF_SPLIT"); return e && std::atoi(e) == 0; }();
     return !off && N > WIDE_SPAN && gstream_ok_dc(c, 6 * N);
 }
@@ -861,7 +873,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
     // heads the workspace; the triangle of
     // group s (fixed window of min(10, N - s) slots, so its shape depends on (N, s) only) is produced in slot s
     const bool xchg = c->xchg;
-    size_t off = xchg ? rec_head(c) + (size_t)N * XCHG_SLOT : 0;
+    size_t off = xchg ? rec_head(c) + (size_t)N * XCHG_SLOT + rec_rem_doubles(c) : 0;
     if (xchg) c->h_xflags.assign(N, 0.0);
     struct Tri { long long src; int lo, w; int lvl = -1, idx = -1, ld = 0; };     // (lvl, idx): the merge node that writes it, if one does; ld: its row stride (0: w + 1)
     const int merge_ld = (c->stream_enabled && mode == 0 && !xchg) ? 64 : 0;      // merge outputs with whole cache lines per row (streamable, k_sweep.h)
@@ -1318,6 +1330,15 @@ int upload_plan(msckf_ctx* c) {
     return MSCKF_OK;
 }
 
+// The dense remainder rows of this context's own batch (k_rem_scatter) and their count words: dRem, or the remainder section of
+// the export record when the batch is planned with split records
+inline bool rem_in_record(const msckf_ctx* c) { return c->xchg_planned && c->xsplit_rows > 0; }
+inline double* rem_rows(msckf_ctx* c) { return rem_in_record(c) ? ptr<double>(c->dRbuf) + rec_rem_off(c) + 1 : ptr<double>(c->dRem); }
+inline int* rem_count(msckf_ctx* c) {
+    return rem_in_record(c) ? reinterpret_cast<int*>(ptr<double>(c->dRbuf) + rec_rem_off(c))
+                            : reinterpret_cast<int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1));   // behind the matrix
+}
+
 int launch_feature(msckf_ctx* c) {
     if (c->F == 0) return MSCKF_OK;
     FeatureArgs a{};
@@ -1367,8 +1388,7 @@ int launch_feature(msckf_ctx* c) {
             r.split = ptr<SplitRec>(c->dSplit); r.n_tracks = nf; r.rows_cap = c->rem_cap;
             r.dc = c->dc; r.N = c->N;
             r.view_ptr = a.view_ptr; r.obs_slot = a.obs_slot; r.blk_off = a.blk_off; r.stack = a.stack; r.stack_f32 = a.stack_f32;
-            r.rank = a.rank; r.accepted = a.accepted; r.out = ptr<double>(c->dRem);
-            r.nrows = reinterpret_cast<int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1));   // behind the matrix
+            r.rank = a.rank; r.accepted = a.accepted; r.out = rem_rows(c); r.nrows = rem_count(c);
             hipLaunchKernelGGL(k_rem_scatter, dim3(nf + 1), dim3(256), 0, st, r);
         }
     };
@@ -1594,12 +1614,19 @@ void fill_gstream_args(msckf_ctx* c, GStreamArgs& a, const double* Tblk, int ban
     // (dtype = f32: the rank-16 products of the P-update on the f32 matrix cores -- but not for a batch with split long tracks: its
     //  dense remainder rows add tens of row blocks, every one an fp32-rounded product against a covariance that keeps shrinking;
     //  tools/soak_holes.py 150 8 f32, (48, 370, <= 22 views): dx off by 2.5e-4 with them, against the mode's 1e-4)
-    a.f32_update = (c->cfg.dtype == MSCKF_DTYPE_F32 && !(c->wide_active && !c->in_merge)) ? 1 : 0;
-    if (c->wide_active && c->rem_direct && !c->t2_early && !c->in_merge) {
-        a.T2 = ptr<double>(c->dRem); a.ldt2 = dc + 1; a.nb2 = (c->rem_cap + 15) / 16;
+    //  (a merge has ONE source of rows, whatever the rank's own last batch looked like -- unless it carries split records: their
+    //  remainder rows, collected into dRem by k_rem_collect, are its second)
+    const bool two = c->in_merge ? c->x_rem_merge : c->wide_active;
+    a.f32_update = (c->cfg.dtype == MSCKF_DTYPE_F32 && !two) ? 1 : 0;
+    const bool early = c->t2_early && two;
+    if (c->in_merge && c->x_rem_merge && !early) {
+        a.T2 = ptr<double>(c->dRem); a.ldt2 = dc + 1; a.nb2 = c->x_rem_blocks;
         a.nb2_dev = reinterpret_cast<const int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1));
+    } else if (!c->in_merge && c->wide_active && c->rem_direct && !early) {
+        a.T2 = rem_rows(c); a.ldt2 = dc + 1; a.nb2 = (c->rem_cap + 15) / 16;
+        a.nb2_dev = rem_count(c);
     }
-    if (c->t2_early && !c->in_merge) { a.P = ptr<double>(c->dPout); a.ldp = d; a.dx0 = ptr<double>(c->dDx); }
+    if (early) { a.P = ptr<double>(c->dPout); a.ldp = d; a.dx0 = ptr<double>(c->dDx); }
     a.stamps = nullptr;
     a.tstamp = c->gs_stamp ? ptr<long long>(c->dGsProg) + 32 : nullptr;
 }
@@ -1632,6 +1659,11 @@ void launch_gain_dense_rows(msckf_ctx* c, const GStreamArgs& a, hipStream_t st) 
 // launch): the update on them runs as a launch of its own, sixteen wavefronts per strip (~7 us per block), on the stream that made
 // them -- beside the band pipeline's leaves, which do not touch P -- from the prior P into P_out / dx (status word 1); the update on
 // the band root, inside the root sweep's launch, then starts from those.
+// row blocks of dense remainder rows from which they get the early launch (MSCKF_T2_EARLY_MIN; below: inside the root's launch)
+int t2_early_min() {
+    static const int m = [] { const char* e = std::getenv("MSCKF_T2_EARLY_MIN"); return e ? std::atoi(e) : 20; }();
+    return m;
+}
 int launch_gain_t2_early(msckf_ctx* c, hipStream_t st) {
     ++c->gs_epoch;
     GStreamArgs a;
@@ -1824,8 +1856,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     const bool direct = c->F > 0 && c->wide_active && c->rem_direct;      // (the dense remainder rows: K6-K7's second source, taken first)
     const bool have_rows = c->root >= 0 || chain || direct;
     {
-        static const int early_min = [] { const char* e = std::getenv("MSCKF_T2_EARLY_MIN"); return e ? std::atoi(e) : 20; }();
-        c->t2_early = direct && with_gain && c->root >= 0 && gstream_ok(c, c->root_band) && (c->rem_cap + 15) / 16 >= early_min;
+        c->t2_early = direct && with_gain && c->root >= 0 && gstream_ok(c, c->root_band) && (c->rem_cap + 15) / 16 >= t2_early_min();
         if (c->t2_early) {
             hipStream_t rs = c->wide_on_stream2 ? c->stream2 : c->stream;
             if ((rc = launch_gain_t2_early(c, rs)) != MSCKF_OK) return rc;
@@ -1895,6 +1926,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     c->ran_gain = with_gain;
     c->acc_override = -1;
     c->acc_from_dev = false;
+    c->x_status1 = false; c->x_rem_last = false;
     ++c->run_serial; c->run_pending = true;
     if (c->res_direct) c->direct_serial = c->run_serial;
     return MSCKF_OK;
@@ -2208,7 +2240,7 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
         if (c->xchg) {
             // a shard without tracks still takes part in the gather: an empty record (no flag, count 0, no gate byte)
             // heads the workspace; the triangles behind it are never read (the merging rank goes by the flags)
-            const size_t need = (rec_head(c) + (size_t)N * rec_slot(c) + 16) * 8;
+            const size_t need = (rec_head(c) + (size_t)N * rec_slot(c) + rec_rem_doubles(c) + 16) * 8;
             if (c->dRbuf.bytes < need) {
                 if (c->dRbuf.p) HIPCHK(c, hipFree(c->dRbuf.p));
                 c->dRbuf.p = nullptr; c->dRbuf.bytes = 0;
@@ -2216,9 +2248,10 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
                 c->dRbuf.bytes = need;
             }
             HIPCHK(c, hipMemsetAsync(c->dRbuf.p, 0, rec_head(c) * 8, c->stream));
+            if (c->xsplit_rows > 0) HIPCHK(c, hipMemsetAsync(ptr<double>(c->dRbuf) + rec_rem_off(c), 0, 8, c->stream));   // no remainder row
             HIPCHK(c, hipStreamSynchronize(c->stream));
             c->xchg_planned = true;
-            c->rbuf_doubles = rec_head(c) + (size_t)N * rec_slot(c);
+            c->rbuf_doubles = rec_head(c) + (size_t)N * rec_slot(c) + rec_rem_doubles(c);
             c->gather_off = c->rbuf_doubles;
         }
         c->have_features = true;
@@ -2327,7 +2360,8 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
     // 90-column band pipeline for all of them: split, each would leave 3 remainder rows to the dense tree
     // ... and so does one whose remainder rows (6 per such track) would be too many for K6-K7 to take as they are: the 90-column
     // pipeline (539 us at 2000 tracks ~ U[2, 15]) beats band pipeline + remainder tree (866 us) there
-    if (Mmax_cls[2] > 0 && n_long == 0 && (2 * n_mid > F || 6 * n_mid > (c->dc > FOLD_RLDS_MAX_W ? c->rem_direct_max_wide : std::min(c->rem_direct_max, 2048)))) {
+    // (not with split records: the whole batch's rule -- msckf_exchange_split_rule -- has decided that for every shard alike)
+    if (Mmax_cls[2] > 0 && n_long == 0 && !(c->xchg && c->xsplit_rows > 0) && (2 * n_mid > F || 6 * n_mid > (c->dc > FOLD_RLDS_MAX_W ? c->rem_direct_max_wide : std::min(c->rem_direct_max, 2048)))) {
         for (int f = 0; f < F; ++f) key_in[f] = (int)((size_t)key_in[f] % NN);
         Mmax_cls[0] = Mmax; Mmax_cls[2] = 0;
     }
@@ -2410,6 +2444,15 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
         // ... and the tree's kernels are at their slowest on windows wider than their LDS holds (N > 31: ~1 ms per level), where the
         // rows are taken as they are up to four times as many
         c->rem_direct = c->split_on && rem_cap <= (c->dc > FOLD_RLDS_MAX_W ? c->rem_direct_max_wide : c->rem_direct_max);
+        if (c->split_on && c->xchg && c->xsplit_rows > 0) {
+            // split records: the rows go to the record's remainder section, whose capacity every rank was told
+            if (rem_cap > c->xsplit_rows) {
+                (void)hipStreamSynchronize(c->stream);
+                c->last_error = "split records: the shard's remainder rows exceed msckf_set_exchange_split's capacity";
+                return MSCKF_ERR_ARG;
+            }
+            c->rem_direct = true;
+        }
         Fs = F + (int)narrow.size() + (int)wide.size();
         h_view.resize(Fs + 1); h_fmin.resize(Fs); h_fmax.resize(Fs);
         c->h_parent.resize(Fs - F);
@@ -2592,8 +2635,9 @@ static int replan_current(msckf_ctx* c, bool one_plan) {
 int msckf_run_compress(msckf_ctx* c) {
     if (!c) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->have_features && c->wide_active) {
+    if (c->have_features && c->wide_active && !c->xchg_planned) {
         // the compressed block leaves this context (msckf_export_block): one plan for every track, the wide ones included
+        // (split records carry the narrow blocks' triangles and the remainder rows as they are)
         if (int rcp = replan_current(c, true)) return rcp;
     }
     return run_pipeline(c, false, nullptr);
@@ -2677,16 +2721,18 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
     c->feat_busy = c->pose_busy = c->main_busy = c->run_pending = false;
     const double tsync = now_us();
     int counters[4] = {0, 0, 0, 0};
-    int status[4] = {0};
+    int status[5] = {0};
     std::vector<unsigned char> acc_sorted;
     const bool gate_done = c->gate_serial == c->run_serial && (!accepted || accepted == c->gate_mask_dst);
     if (gate_done) std::memcpy(counters, c->gate_cnt, sizeof(counters));
     else if (int rc0 = gate_counts(c, counters, &acc_sorted, true)) return rc0;
-    if (c->ran_gain) std::memcpy(status, c->hRes, 16);
+    if (c->ran_gain) std::memcpy(status, c->hRes, 20);
+    if (!c->x_rem_last) status[4] = 0;
     const int n_acc = c->acc_from_dev ? status[2] : (c->acc_override >= 0) ? c->acc_override : counters[0];
     if (!(c->ran_gain && n_acc > 0)) status[0] = status[1] = 0;
     int rc = (n_acc == 0) ? MSCKF_NOOP : MSCKF_OK;
-    if (rc == MSCKF_OK && c->ran_gain && (status[0] != 0 || ((c->gain_blocked || c->wide_active) && status[1] != 0))) rc = MSCKF_ERR_NOT_SPD;
+    if (rc == MSCKF_OK && c->ran_gain && (status[0] != 0 || ((c->gain_blocked || c->wide_active || c->x_status1) && status[1] != 0))) rc = MSCKF_ERR_NOT_SPD;
+    if (rc == MSCKF_OK && (status[4] & 2)) { c->last_error = "split records: more remainder rows than the merge takes"; rc = MSCKF_ERR_STATE; }
     if (rc == MSCKF_ERR_NOT_SPD && status[0] == 3) {       // the mirror of the status word in host memory was never written
         c->last_error = "K6-K7 did not report a status";
         rc = MSCKF_ERR_HIP;
@@ -2695,13 +2741,13 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
         static const bool fake = [] { const char* e = std::getenv("MSCKF_DEBUG_FAKE_TIMEOUT"); return e && std::atoi(e) == 1; }();
         if (fake && !c->fake_timeout_done && rc == MSCKF_OK && c->ran_gain && c->gs_fused_last) { c->fake_timeout_done = true; status[0] = 2; rc = MSCKF_ERR_NOT_SPD; }
     }
-    if (rc == MSCKF_ERR_NOT_SPD && (status[0] == 2 || (c->wide_active && status[1] == 2))) {       // k_gain_stream gave up waiting for rows of T or for another workgroup
+    if (rc == MSCKF_ERR_NOT_SPD && (status[0] == 2 || ((c->wide_active || c->x_status1) && status[1] == 2))) {       // k_gain_stream gave up waiting for rows of T or for another workgroup
         // The workgroups of k_root_gain / k_gain_stream wait for each other inside their launch; that they are all resident is
         // argued from their LDS footprint and the device's CU count, not promised by HIP: a partitioned or busy
         // device can keep one out until the 0.5 s bound.  ONE retry on kernels that never wait inside a launch (separate merge
         // levels and root, round 3's K6-K7 launches), and the context stays on them.  Not with split long tracks in the batch
         // (their second source of rows needs the sequential block update).
-        if (c->have_features && !c->split_on && !c->retry_plain && c->gs_enabled) {
+        if (c->have_features && !c->split_on && !c->x_status1 && !c->retry_plain && c->gs_enabled) {
             c->retry_plain = true;
             c->gs_enabled = false; c->stream_enabled = false;
             if (int r2 = replan_current(c, false)) return r2;
@@ -3173,7 +3219,12 @@ int msckf_export_block(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accep
     return MSCKF_OK;
 }
 
-struct MergeScope { msckf_ctx* c; explicit MergeScope(msckf_ctx* c_) : c(c_) { c->in_merge = true; } ~MergeScope() { c->in_merge = false; } };
+// (x_rem_merge describes the merge being launched only: a later merge of another kind must not inherit it)
+struct MergeScope {
+    msckf_ctx* c;
+    explicit MergeScope(msckf_ctx* c_) : c(c_) { c->in_merge = true; c->x_rem_merge = false; }
+    ~MergeScope() { c->in_merge = false; c->x_rem_merge = false; }
+};
 
 int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int device_ptr,
                          int32_t total_accepted) {
@@ -3183,6 +3234,10 @@ int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->N, dc = c->dc;
     const size_t blk = (size_t)dc * (dc + 1);
+    // ONE source of rows; status words 1 and 4 are this merge's (an earlier merge of split records wrote them)
+    c->t2_early = false; c->x_status1 = false; c->x_rem_last = false;
+    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 1, 0, 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 4, 0, 4, c->stream));
     // workspace: gathered blocks + merge outputs, behind the local plan's region
     std::vector<FoldNode> nodes;
     std::vector<std::pair<int, int>> levels;
@@ -3270,7 +3325,102 @@ int msckf_band_rule(const msckf_ctx* c, int32_t N, int32_t max_span) {
 }
 
 size_t msckf_group_record_doubles(const msckf_ctx* c) {
-    return c ? rec_head(c) + (size_t)c->N * rec_slot(c) : 0;
+    return c ? rec_head(c) + (size_t)c->N * rec_slot(c) + rec_rem_doubles(c) : 0;
+}
+
+int msckf_set_exchange_split(msckf_ctx* c, int32_t rows_per_record, int32_t rows_total) {
+    if (!c || rows_per_record < 0 || rows_total < 0 || rows_per_record > 16 * GS_MAX_NB2) return MSCKF_ERR_ARG;
+    // (whole row blocks: k_rem_scatter pads a shard's rows with zero rows up to the next multiple of 16)
+    c->xsplit_rows = (rows_per_record + 15) / 16 * 16;
+    c->xsplit_total = rows_per_record > 0 ? rows_total : 0;
+    c->have_features = false;             // the record layout changed: the next msckf_set_features plans afresh
+    c->plan_valid = false;
+    c->x_plan_valid = false;
+    c->ran = false;
+    return MSCKF_OK;
+}
+
+// The whole batch's decision for split records: the classification of msckf_set_features, taken over ALL tracks, so that
+// every rank gets the same answer from the same arguments without a collective.  ctx may be null (defaults).
+int msckf_exchange_split_rule(const msckf_ctx* c, int32_t N, int32_t F, const int32_t* view_ptr, const int32_t* obs_slot,
+                              int32_t n_shards, const int32_t* bounds, int32_t out[4], uint8_t* flags) {
+    if (!out || N < 1 || F < 0 || n_shards < 1 || n_shards > 64 || !bounds || (F > 0 && (!view_ptr || !obs_slot))) return MSCKF_ERR_ARG;
+    if (bounds[0] != 0 || bounds[n_shards] != F) return MSCKF_ERR_ARG;
+    for (int r = 0; r < n_shards; ++r) if (bounds[r + 1] < bounds[r]) return MSCKF_ERR_ARG;
+    if (F > 0 && view_ptr[0] != 0) return MSCKF_ERR_ARG;
+    for (int f = 0; f < F; ++f) if (view_ptr[f + 1] <= view_ptr[f]) return MSCKF_ERR_ARG;
+    for (int i = 0; F > 0 && i < view_ptr[F]; ++i) if (obs_slot[i] < 0 || obs_slot[i] >= N) return MSCKF_ERR_ARG;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    const int dc = 6 * N;
+    bool can = N > WIDE_SPAN;
+    if (c) can = can && !(c->cfg.flags & (MSCKF_FLAG_TREE_PLAN | MSCKF_FLAG_BAND_ONLY)) && gstream_ok_dc(c, dc);
+    else {
+        const int nb = (dc + 15) / 16, ns = nb + 1;
+        can = can && ns <= GS_MAX_NS && gstream_lds_doubles(ns, nb) * 8 <= (size_t)(LDS_MAX_BYTES - 1024);
+    }
+    {
+        static const bool off = [] { const char* e = std::getenv("MSCKF_SPLIT"); return e && std::atoi(e) == 0; }();
+        can = can && !off;
+    }
+    const int direct_max = c ? (dc > FOLD_RLDS_MAX_W ? c->rem_direct_max_wide : c->rem_direct_max)
+                             : (dc > FOLD_RLDS_MAX_W ? 16 * GS_MAX_NB2 : msckf_ctx::REM_DIRECT_DEFAULT);
+    // per track: span, and for a long one its view groups (as msckf_set_features cuts them)
+    int n_mid = 0, n_long = 0, n_split = 0, max_span = 0, band_span = 0;
+    bool all_split = true;
+    std::vector<long long> rows(n_shards, 0);
+    std::vector<int> first_slots;                         // (per track: the first slots of what the band plan will see)
+    std::vector<int> fs_ptr(1, 0);
+    for (int f = 0; f < F; ++f) {
+        const int a = view_ptr[f], b = view_ptr[f + 1], M = b - a;
+        int lo = N, hi = -1;
+        bool ordered = true;
+        for (int i = a; i < b; ++i) { if (obs_slot[i] < hi) ordered = false; lo = std::min(lo, obs_slot[i]); hi = std::max(hi, obs_slot[i]); }
+        const int span = hi - lo + 1, ng0 = (span + SPLIT_GSLOTS - 1) / SPLIT_GSLOTS;
+        max_span = std::max(max_span, span);
+        if (span > 15) ++n_long; else if (span > WIDE_SPAN) ++n_mid;
+        if (span <= WIDE_SPAN) { band_span = std::max(band_span, span); first_slots.push_back(lo); fs_ptr.push_back((int)first_slots.size()); continue; }
+        if (!(ordered && M <= 31 && ng0 <= SPLIT_MAXG)) { all_split = false; first_slots.push_back(lo); fs_ptr.push_back((int)first_slots.size()); continue; }
+        ++n_split;
+        int ng = 0, v = 0;
+        for (int g0 = 0; g0 < ng0; ++g0) {
+            const int bnd = lo + (int)(((long long)(g0 + 1) * span) / ng0);
+            const int v0 = v;
+            while (v < M && obs_slot[a + v] < bnd) ++v;
+            if (v == v0) continue;
+            if (v - v0 >= 2) {                            // a narrow block: an ordinary track of the band plan
+                first_slots.push_back(obs_slot[a + v0]);
+                band_span = std::max(band_span, obs_slot[a + v - 1] - obs_slot[a + v0] + 1);
+            }
+            ++ng;
+        }
+        fs_ptr.push_back((int)first_slots.size());
+        int r = 0;
+        while (r + 1 < n_shards && f >= bounds[r + 1]) ++r;
+        rows[r] += 3 * ng;                                // (3 (groups - 1) rows when H_f has full rank; k_feature.h reserves 3 per group)
+    }
+    long long cap = 0, total = 0;
+    for (int r = 0; r < n_shards; ++r) { cap = std::max(cap, rows[r]); total += rows[r]; }
+    bool split = can && n_split > 0 && all_split;
+    // (a batch MOST of whose tracks span 11 - 15 slots and none more keeps the 90-column pipeline, as in msckf_set_features)
+    if (split && n_long == 0 && (2 * n_mid > F || 6 * n_mid > (dc > FOLD_RLDS_MAX_W ? direct_max : std::min(direct_max, 2048)))) split = false;
+    if (split && total > direct_max) split = false;       // (no k_fold tree of the remainder rows on the merging rank)
+    out[0] = split ? 1 : 0;
+    out[1] = split ? band_span : max_span;
+    out[2] = split ? (int)((cap + 15) / 16 * 16) : 0;
+    out[3] = split ? (int)total : 0;
+    if (flags) {
+        std::memset(flags, 0, (size_t)n_shards * N);
+        for (int r = 0; r < n_shards; ++r)
+            for (int f = bounds[r]; f < bounds[r + 1]; ++f) {
+                if (split) { for (int k = fs_ptr[f]; k < fs_ptr[f + 1]; ++k) flags[(size_t)r * N + first_slots[k]] = 1; }
+                else {
+                    int lo = N;
+                    for (int i = view_ptr[f]; i < view_ptr[f + 1]; ++i) lo = std::min(lo, obs_slot[i]);
+                    flags[(size_t)r * N + lo] = 1;
+                }
+            }
+    }
+    return MSCKF_OK;
 }
 
 int msckf_export_groups(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accepted) {
@@ -3278,7 +3428,7 @@ int msckf_export_groups(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_acce
     if (!c->ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = msckf_group_record_doubles(c) * 8;
-    if (c->F == 0 || c->root < 0) {       // no tracks in this shard: all flags 0
+    if (c->F == 0 || (c->root < 0 && !rem_in_record(c))) {       // no tracks in this shard: all flags 0
         if (device_ptr) HIPCHK(c, hipMemsetAsync(dst, 0, bytes, c->stream));
         else std::memset(dst, 0, bytes);
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3361,6 +3511,21 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
     if (device_ptr) recs = static_cast<const double*>(records);
     else HIPCHK(c, hipMemcpyAsync(rb + o_rec, records, (size_t)n_rec * rec * 8, hipMemcpyHostToDevice, c->stream));
     const long long rec_base = (long long)(recs - rb);
+    // status words 1 and 4 are this merge's: nothing of the rank's own earlier batch may be read as its outcome
+    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 1, 0, 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 4, 0, 4, c->stream));
+    // split records (msckf_set_exchange_split): their remainder rows are K6-K7's second source, collected into dRem; from
+    // t2_early_min() row blocks on the update on them is a launch of its own on the second stream, beside the group folds
+    // and the root sweep (as launch_gain_t2_early on one GPU), the update on the root starts from its P_out / dx
+    c->x_rem_merge = c->xsplit_rows > 0;
+    bool early = false;
+    if (c->x_rem_merge) {
+        if (!gstream_ok_dc(c, dc)) { c->last_error = "split records need the streamed K6-K7"; return MSCKF_ERR_STATE; }
+        long long rows = (long long)n_rec * c->xsplit_rows;
+        if (c->xsplit_total > 0) rows = std::min<long long>(rows, c->xsplit_total);
+        c->x_rem_blocks = (int)std::min<long long>(GS_MAX_NB2, (rows + 15) / 16);
+        early = c->x_rem_blocks >= t2_early_min();
+    }
     // which groups does each record carry?  (N flags and the accepted count at the head of every record)
     std::vector<double> key((size_t)n_rec * N);
     bool count_on_device = false;
@@ -3416,7 +3581,7 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         c->x_n_merges = (int)c->x_snodes.size();
         // the merge level rides in the root's launch and streams its rows to the root (as the local plan's last level does)
         c->x_streamed = xs && c->x_n_merges >= 1 && c->x_n_merges <= 64 && groups.size() > 1 && root_gain_ok(c, XW) &&
-                        2 * (2 + (dc + 15) / 16 + c->x_n_merges) <= c->n_cu;
+                        2 * (2 + (dc + 15) / 16 + c->x_n_merges) <= c->n_cu && !early;     // (an early update: the root sweep alone)
         if (!groups.empty()) {
             SweepNode r{};
             r.fold_begin = fold_base + (int)fl.size();
@@ -3486,6 +3651,50 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         c->x_key = key; c->x_nrec = n_rec; c->x_root_off = o_root; c->x_zero_off = o_zero; c->x_rec_base = rec_base;
         c->x_plan_valid = true;
     }
+    if (c->x_snodes.empty()) early = false;          // (remainder rows alone: one launch on them, status word 0)
+    c->t2_early = early;
+    c->x_status1 = early; c->x_rem_last = c->x_rem_merge;
+    if (c->x_rem_merge) {
+        if (early) {
+            hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, ptr<int>(c->dStatus) + 4, 1);
+            HIPCHK(c, hipGetLastError());
+        }
+        RemCollectArgs ra{};
+        ra.recs = recs; ra.rec_stride = (long long)rec; ra.rem_off = (long long)rec_rem_off(c); ra.rec_rows = c->xsplit_rows;
+        ra.n_rec = n_rec; ra.ld = dc + 1; ra.max_rows = 16 * c->x_rem_blocks;
+        ra.out = ptr<double>(c->dRem);
+        ra.nrows = reinterpret_cast<int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1));
+        ra.status = ptr<int>(c->dStatus);
+        hipLaunchKernelGGL(k_rem_collect, dim3(n_rec + 1), dim3(256), 0, c->stream, ra);
+        HIPCHK(c, hipGetLastError());
+        if (early) {
+            HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+            if (int rce = launch_gain_t2_early(c, c->stream2)) return rce;
+            {   // MSCKF_DEBUG_FAKE_TIMEOUT=1 (tests): the first early update of a merge reads as timed out
+                static const bool fake = [] { const char* e = std::getenv("MSCKF_DEBUG_FAKE_TIMEOUT"); return e && std::atoi(e) == 1; }();
+                if (fake && !c->fake_timeout_done) {
+                    c->fake_timeout_done = true;
+                    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream2, ptr<int>(c->dStatus) + 1, 2);
+                    HIPCHK(c, hipGetLastError());
+                }
+            }
+            HIPCHK(c, hipEventRecord(c->ev_rem, c->stream2));
+        }
+    }
+    if (c->x_snodes.empty() && c->x_rem_merge) {     // no triangle anywhere, remainder rows only: K6-K7 on them alone
+        ++c->gs_epoch;
+        GStreamArgs ga;
+        fill_gstream_args(c, ga, nullptr, dc, false);
+        launch_gain_dense_rows(c, ga, c->stream);
+        HIPCHK(c, hipGetLastError());
+        if (int rcm = collect_masks(c, recs, (long long)rec, n_rec)) return rcm;
+        c->ran = true; c->ran_gain = true;
+        c->acc_override = total_accepted;
+        c->acc_from_dev = count_on_device;
+        ++c->run_serial; c->run_pending = true;
+        return MSCKF_OK;
+    }
     if (c->x_snodes.empty()) {            // no shard has a track: nothing to update
         if (!count_on_device) {
             hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, ptr<int>(c->dStatus) + 2, 0);
@@ -3502,7 +3711,7 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         int ms = 0;
         for (int i = 0; i < c->x_n_merges; ++i) ms = std::max(ms, c->x_snodes[i].nsteps);
         const int rs = c->x_snodes.back().nsteps;
-        const bool fused = root_gain_w_ok(c, XW);               // the root sweep and K6-K7 in one launch (k_root_gain_w)
+        const bool fused = root_gain_w_ok(c, XW) && !early;     // the root sweep and K6-K7 in one launch (k_root_gain_w)
         if (xmode == 1) {
             if (c->x_n_merges > 0) launch_wsweep<4>(c, nb, c->x_n_merges, WS_RC_LOG2_4, ms, rb + c->x_zero_off);
             if (!fused) launch_wsweep<4>(c, nb + c->x_n_merges, 1, WS_RC_LOG2_4, rs, rb + c->x_zero_off);
@@ -3511,6 +3720,8 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
             if (!fused) launch_wsweep<6>(c, nb + c->x_n_merges, 1, WS_RC_LOG2_6, rs, rb + c->x_zero_off);
         }
         HIPCHK(c, hipGetLastError());
+        if (early) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));      // (its P_out / dx are what the update below starts from)
+        if (c->x_rem_merge && !fused && !gstream_ok(c, XW)) { c->last_error = "split records need the streamed K6-K7"; return MSCKF_ERR_STATE; }
         int rcg;
         if (fused && xmode == 1) rcg = launch_root_and_gain_w<4>(c, nb + c->x_n_merges, rs, WS_RC_LOG2_4, rb + c->x_zero_off, rb + c->x_root_off, XW);
         else if (fused) rcg = launch_root_and_gain_w<6>(c, nb + c->x_n_merges, rs, WS_RC_LOG2_6, rb + c->x_zero_off, rb + c->x_root_off, XW);
@@ -3531,7 +3742,7 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
     a.stamps = nullptr;
     a.zero = rb + c->x_zero_off;
     const dim3 block(64 * SWEEP_NW * SWEEP_WPF);
-    const bool fused = root_gain_ok(c, XW) && !c->x_root_flush.empty();
+    const bool fused = root_gain_ok(c, XW) && !c->x_root_flush.empty() && !early;
     const bool ride_on = fused && c->x_streamed;
     if (c->x_n_merges > 0 && !ride_on) {
         a.node_base = nb;
@@ -3551,6 +3762,8 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
     } else {
         hipLaunchKernelGGL((k_sweep<SWEEP_NW, SWEEP_WPF, SWEEP_P2P>), dim3(1), block, sweep_lds_bytes(dc, SWEEP_NW, SWEEP_WPF), c->stream, a);
         HIPCHK(c, hipGetLastError());
+        if (early) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));      // (its P_out / dx are what the update below starts from)
+        if (c->x_rem_merge && !gstream_ok(c, XW)) { c->last_error = "split records need the streamed K6-K7"; return MSCKF_ERR_STATE; }
         if (gstream_ok(c, XW)) rc = launch_gain_stream(c, rb + c->x_root_off, XW);
         else rc = launch_gain(c, rb + c->x_root_off);
     }
@@ -3721,15 +3934,20 @@ int msckf_get_shared_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* ac
     const size_t total = c->x_bounds.empty() ? 0 : (size_t)c->x_bounds.back();
     HIPCHK(c, hipMemcpyAsync(c->hRes, c->dResArena.p, c->res_mask_off + total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    int status[4];
-    std::memcpy(status, c->hRes, 16);
+    int status[5];
+    std::memcpy(status, c->hRes, 20);
     const int dc = c->dc;
     // (as launch_gain decides; k_gain_stream -- dtype f64 -- uses the first status word only)
     const bool blocked = !(c->gs_enabled && (dc + 15) / 16 + 1 <= GS_MAX_NS) &&
                          dc > 4 * CHOL_TILE_MAX_NT && dc <= 2 * GAIN_BLK && dc - GAIN_BLK >= 4;
     const int n_acc = status[2];
     int rc = (n_acc <= 0) ? MSCKF_NOOP : MSCKF_OK;
-    if (rc == MSCKF_OK && (status[0] != 0 || (blocked && status[1] != 0))) rc = status[0] == 2 ? MSCKF_ERR_HIP : MSCKF_ERR_NOT_SPD;
+    // (status word 4, written by merges of split records: bit 0 -- a launch of the merge, the early update on the remainder rows,
+    //  wrote word 1; bit 1 -- the records held more remainder rows than the merge takes)
+    const bool word1 = blocked || (status[4] & 1);
+    if (rc == MSCKF_OK && (status[0] != 0 || (word1 && status[1] != 0)))
+        rc = (status[0] == 2 || ((status[4] & 1) && status[1] == 2)) ? MSCKF_ERR_HIP : MSCKF_ERR_NOT_SPD;
+    if (rc == MSCKF_OK && (status[4] & 2)) rc = MSCKF_ERR_STATE;
     const char* hres = static_cast<const char*>(c->hRes);
     if (dx) {
         if (rc == MSCKF_OK) std::memcpy(dx, hres + c->res_dx_off, d * 8);

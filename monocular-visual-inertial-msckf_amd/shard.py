@@ -179,8 +179,8 @@ def exchange_unique_id(engine, rank: int, world: int, path: str, timeout_s: floa
 
 
 class RcclShardedUpdate:
-    """One sharded update per `step()`: K1-K5 on the local shard, ONE RCCL gather of the group records (or root
-    blocks) to rank 0, merge + K6-K7 there, ONE RCCL broadcast of the result range
+    """One sharded update per `step()`: K1-K5 on the local shard, ONE RCCL gather of the group records (split records when
+    the batch has long tracks the rule admits; else root blocks) to rank 0, merge + K6-K7 there, ONE RCCL broadcast of the result range
     `status | dx | P+ | gate bytes of the whole batch` (`msckf_set_exchange_mask`: the shards' gate results ride in
     their records).  Everything is enqueued on the engine's stream; a step returns without waiting for the device.
     `result()` is the same call on every rank and yields the same status everywhere (0 updated / 1 no-op; a
@@ -195,6 +195,7 @@ class RcclShardedUpdate:
             except OSError:
                 pass
         self.groups = False
+        self.split = False
         self.count = 0
         self.flags = None
         self.recv = 0
@@ -204,9 +205,20 @@ class RcclShardedUpdate:
         e = self.e
         shards = partition_features(prob.view_ptr, self.world)
         self.bounds = np.array([s[0] for s in shards] + [shards[-1][1]], dtype=np.int32)
+        # long tracks: split records when the whole batch's rule admits them (the same answer on every rank), their narrow
+        # blocks' triangles in the group slots, their remainder rows in a section of their own
+        # (`groups`: the batch's tracks as they are fit the band pipeline; `split`: split records -- with an engine that has them)
+        split_rule = getattr(e, "exchange_split_rule", None)
+        rule = split_rule(prob, shards) if split_rule else {"split": False}
+        self.split = rule["split"]
         self.groups = bool(e.band_ok(prob))
-        e.set_group_exchange(self.groups)
-        e.set_exchange_span(e.max_span(prob) if self.groups else 0)    # every rank: the sweep mode of the whole batch
+        e.set_group_exchange(self.groups or self.split)
+        if self.split:
+            e.set_exchange_split(rule["rows"], rule["total"])
+        elif split_rule:
+            e.set_exchange_split(0)
+        # every rank: the sweep mode of the whole batch (after the split: its narrow blocks')
+        e.set_exchange_span(rule["span"] if self.split else (e.max_span(prob) if self.groups else 0))
         e.set_exchange_mask(self.bounds)
         lo, hi = shards[self.rank]
         e.load(prob.subset(lo, hi))
@@ -214,9 +226,9 @@ class RcclShardedUpdate:
         self.shard = (lo, hi)
         self.F_total = int(prob.F)
         self.mask_doubles = (int(np.diff(self.bounds).max()) + 7) // 8
-        if self.groups:
+        if self.groups or self.split:
             self.count = e.group_record_doubles()
-            self.flags = shard_group_flags(prob, shards)
+            self.flags = rule["flags"] if self.split else shard_group_flags(prob, shards)
         else:
             # fallback exchange (tracks wider than the sweep tiles, merge tree forced): root blocks [R | Q^T r], the
             # shard's accepted count and its gate bytes, staged through host memory on both sides
@@ -230,7 +242,7 @@ class RcclShardedUpdate:
     def step(self):
         e = self.e
         e.run_compress()
-        if self.groups:
+        if self.groups or self.split:
             e.comm_gather(e.device_pointer(3), self.recv, self.count, 0)        # the record lies at the head of the workspace
             if self.rank == 0:
                 e.merge_groups_flags(self.recv, self.world, self.flags)          # no read-back: flags from the partition

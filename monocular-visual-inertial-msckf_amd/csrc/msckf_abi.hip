@@ -311,7 +311,7 @@ struct msckf_ctx {
     bool x_rem_merge = false;             // the merge being launched carries split records: K6-K7 has TWO sources of rows
     int x_rem_blocks = 0;                 // ... row blocks of 16 the merge's dense rows may fill (dRem)
     bool x_rem_last = false;              // the last run was such a merge (status word 4 is its)
-    bool x_status1 = false;               // status word 1 was written by a launch of the last merge (its early update)
+    bool x_status1 = false;               // status word 1 was written by a launch of the last run or merge (an early update or a chain)
     std::vector<double> h_xflags;         // [N] 1.0 where this shard has tracks starting at the slot
     std::vector<double> x_key;            // flags of the last merged records (plan cache of msckf_run_merge_groups)
     int x_nrec = 0;
@@ -1602,11 +1602,15 @@ void fill_gstream_args(msckf_ctx* c, GStreamArgs& a, const double* Tblk, int ban
     a.ex = ptr<double>(c->dGsEx); a.exflag = ptr<unsigned long long>(c->dGsFlag);
     a.dx = ptr<double>(c->dDx); a.Pout = ptr<double>(c->dPout); a.ldo = d;
     a.status = ptr<int>(c->dStatus);
+    const bool two = c->in_merge ? c->x_rem_merge : c->wide_active;
+    const bool early = c->t2_early && two;
     if (c->res_direct && c->want_direct) {
         char* h = static_cast<char*>(c->hRes);
         a.status_h = reinterpret_cast<int*>(h); a.dx_h = reinterpret_cast<double*>(h + c->res_dx_off);
         a.Pout_h = reinterpret_cast<double*>(h + c->res_p_off);
-        reinterpret_cast<int*>(h)[0] = 3; reinterpret_cast<int*>(h)[1] = 0; reinterpret_cast<int*>(h)[2] = 0;     // 3: not written
+        // 3: not written.  (Word 1 is the early launch's mirror, seeded by launch_gain_t2_early: that launch is in flight by now.)
+        reinterpret_cast<int*>(h)[0] = 3; reinterpret_cast<int*>(h)[2] = 0;
+        if (!early) reinterpret_cast<int*>(h)[1] = 0;
     }
     a.sigma2 = c->sigma * c->sigma;
     a.d = d; a.dc = dc; a.nb = nb; a.ns = nb + 1; a.ncb = gstream_ncb(dc, band);
@@ -1616,9 +1620,7 @@ void fill_gstream_args(msckf_ctx* c, GStreamArgs& a, const double* Tblk, int ban
     //  tools/soak_holes.py 150 8 f32, (48, 370, <= 22 views): dx off by 2.5e-4 with them, against the mode's 1e-4)
     //  (a merge has ONE source of rows, whatever the rank's own last batch looked like -- unless it carries split records: their
     //  remainder rows, collected into dRem by k_rem_collect, are its second)
-    const bool two = c->in_merge ? c->x_rem_merge : c->wide_active;
     a.f32_update = (c->cfg.dtype == MSCKF_DTYPE_F32 && !two) ? 1 : 0;
-    const bool early = c->t2_early && two;
     if (c->in_merge && c->x_rem_merge && !early) {
         a.T2 = ptr<double>(c->dRem); a.ldt2 = dc + 1; a.nb2 = c->x_rem_blocks;
         a.nb2_dev = reinterpret_cast<const int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1));
@@ -1673,6 +1675,10 @@ int launch_gain_t2_early(msckf_ctx* c, hipStream_t st) {
     c->t2_early = keep;
     a.status = ptr<int>(c->dStatus) + 1;
     a.status_h = nullptr; a.dx_h = nullptr; a.Pout_h = nullptr; a.tstamp = nullptr;
+    if (c->res_direct && c->want_direct) {      // the direct result reads status word 1 from hRes: mirror it there (3: not written)
+        a.status_h = static_cast<int*>(c->hRes) + 1;
+        *a.status_h = 3;
+    }
     launch_gain_dense_rows(c, a, st);
     HIPCHK(c, hipGetLastError());
     return MSCKF_OK;
@@ -1855,6 +1861,11 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     // K6-K7 beside the root sweep: the band plan's k_sweep root with the flusher wavefront and the update's strips in ONE launch
     const bool direct = c->F > 0 && c->wide_active && c->rem_direct;      // (the dense remainder rows: K6-K7's second source, taken first)
     const bool have_rows = c->root >= 0 || chain || direct;
+    const bool gs = with_gain && c->F > 0 && have_rows && gstream_ok(c, c->root_band);
+    // (split long tracks' second source of rows -- a tree's root or triangles, or the dense rows -- needs the streamed K6-K7)
+    if ((chain || direct) && with_gain && !gs) { c->last_error = "split long tracks need the streamed K6-K7"; return MSCKF_ERR_STATE; }
+    // (known before the early launch below: that launch mirrors its status word into hRes when this run's result is direct)
+    c->res_direct = c->want_direct && c->gate_direct && gs && !chain;       // (a second update behind the first writes the HBM copies only)
     {
         c->t2_early = direct && with_gain && c->root >= 0 && gstream_ok(c, c->root_band) && (c->rem_cap + 15) / 16 >= t2_early_min();
         if (c->t2_early) {
@@ -1863,8 +1874,6 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
             if (c->wide_on_stream2) HIPCHK(c, hipEventRecord(c->ev_rem, c->stream2));
         }
     }
-    const bool gs = with_gain && c->F > 0 && have_rows && gstream_ok(c, c->root_band);
-    if (chain && with_gain && !gs) { c->last_error = "split long tracks need the streamed K6-K7"; return MSCKF_ERR_STATE; }
     // (behind an early update on the dense remainder rows the root sweep runs as a launch of its own, BESIDE that update, and the update
     //  on its rows follows both: in one launch with it the sweep would wait for the remainder rows' update too -- a frame of 300 tracks
     //  ~ U[2, 30]: 695 -> ~610 us)
@@ -1882,7 +1891,6 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     }
     if (c->t2_early && c->wide_on_stream2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));     // (its P_out / dx are what the update below starts from)
     c->gs_fused_last = beside;
-    c->res_direct = c->want_direct && c->gate_direct && gs && !chain;       // (a second update behind the first writes the HBM copies only)
     if (beside && c->sweep_mode > 0) {
         const SweepNode& rn = c->snodes.back();
         const double* zero = ptr<double>(c->dRbuf) + c->zero_off;
@@ -1926,7 +1934,8 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     c->ran_gain = with_gain;
     c->acc_override = -1;
     c->acc_from_dev = false;
-    c->x_status1 = false; c->x_rem_last = false;
+    // status word 1 is this run's only where a launch of this run wrote it; otherwise it is stale (nothing resets it between runs)
+    c->x_status1 = with_gain && (chain || c->t2_early); c->x_rem_last = false;
     ++c->run_serial; c->run_pending = true;
     if (c->res_direct) c->direct_serial = c->run_serial;
     return MSCKF_OK;
@@ -2731,9 +2740,9 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
     const int n_acc = c->acc_from_dev ? status[2] : (c->acc_override >= 0) ? c->acc_override : counters[0];
     if (!(c->ran_gain && n_acc > 0)) status[0] = status[1] = 0;
     int rc = (n_acc == 0) ? MSCKF_NOOP : MSCKF_OK;
-    if (rc == MSCKF_OK && c->ran_gain && (status[0] != 0 || ((c->gain_blocked || c->wide_active || c->x_status1) && status[1] != 0))) rc = MSCKF_ERR_NOT_SPD;
+    if (rc == MSCKF_OK && c->ran_gain && (status[0] != 0 || ((c->gain_blocked || c->x_status1) && status[1] != 0))) rc = MSCKF_ERR_NOT_SPD;
     if (rc == MSCKF_OK && (status[4] & 2)) { c->last_error = "split records: more remainder rows than the merge takes"; rc = MSCKF_ERR_STATE; }
-    if (rc == MSCKF_ERR_NOT_SPD && status[0] == 3) {       // the mirror of the status word in host memory was never written
+    if (rc == MSCKF_ERR_NOT_SPD && (status[0] == 3 || (c->x_status1 && status[1] == 3))) {   // a mirror of a status word in host memory was never written
         c->last_error = "K6-K7 did not report a status";
         rc = MSCKF_ERR_HIP;
     }
@@ -2741,7 +2750,7 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
         static const bool fake = [] { const char* e = std::getenv("MSCKF_DEBUG_FAKE_TIMEOUT"); return e && std::atoi(e) == 1; }();
         if (fake && !c->fake_timeout_done && rc == MSCKF_OK && c->ran_gain && c->gs_fused_last) { c->fake_timeout_done = true; status[0] = 2; rc = MSCKF_ERR_NOT_SPD; }
     }
-    if (rc == MSCKF_ERR_NOT_SPD && (status[0] == 2 || ((c->wide_active || c->x_status1) && status[1] == 2))) {       // k_gain_stream gave up waiting for rows of T or for another workgroup
+    if (rc == MSCKF_ERR_NOT_SPD && (status[0] == 2 || (c->x_status1 && status[1] == 2))) {       // k_gain_stream gave up waiting for rows of T or for another workgroup
         // The workgroups of k_root_gain / k_gain_stream wait for each other inside their launch; that they are all resident is
         // argued from their LDS footprint and the device's CU count, not promised by HIP: a partitioned or busy
         // device can keep one out until the 0.5 s bound.  ONE retry on kernels that never wait inside a launch (separate merge
@@ -2809,8 +2818,8 @@ int msckf_commit_covariance(msckf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int n_acc = c->acc_from_dev ? status[2] : (c->acc_override >= 0) ? c->acc_override : counters[0];
     if (n_acc == 0) return MSCKF_NOOP;
-    if (status[0] == 2 || (c->wide_active && status[1] == 2)) return MSCKF_ERR_HIP;   // k_gain_stream timed out
-    if (status[0] != 0 || ((c->gain_blocked || c->wide_active) && status[1] != 0)) return MSCKF_ERR_NOT_SPD;
+    if (status[0] == 2 || (c->x_status1 && status[1] == 2)) return MSCKF_ERR_HIP;   // k_gain_stream timed out
+    if (status[0] != 0 || ((c->gain_blocked || c->x_status1) && status[1] != 0)) return MSCKF_ERR_NOT_SPD;
     HIPCHK(c, hipMemcpyAsync(c->dP.p, c->dPout.p, (size_t)c->d * c->d * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MSCKF_OK;

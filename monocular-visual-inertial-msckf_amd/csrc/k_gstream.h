@@ -41,6 +41,7 @@
 #include "k_gain.h"
 #include "k_sweep.h"
 #include "k_wsweep.h"
+#include "k_lsweep.h"
 
 namespace msckf {
 
@@ -566,6 +567,21 @@ __global__ __launch_bounds__(64 * (NFM + 1)) void k_root_gain_m(SweepArgs sp, GS
     if (b == 0) sweep_body<NFR, 1, false, true, NFM - NFR>(sp, 0);
     else if (b <= gp.ns) gain_stream_body<NFM + 1, NFM, TPW>(gp, b - 1);
     else sweep_body<NFM, 1, false, true>(mp, b - 1 - gp.ns);
+}
+
+// The band plan's whole K5-K7 in ONE launch (the headline's form: one merge level, 60-column leaves of one round): workgroups
+// [0, nl) are the leaves (k_lsweep's 60-column tile without the prefetch, whose second tile does not fit the 168 registers of nine
+// wavefronts, plus a flusher that publishes their rows in blocks of 8), [nl, nl + nm) the merge nodes -- gated on their leaves'
+// progress words as the root is on theirs (SweepArgs::gate_per_node) and streaming to it --, then the root sweep, then the strips.
+// Every workgroup waits only for workgroups of lower index (the strips also for each other), so the root's first fold starts a
+// few dozen macro steps after the leaves do instead of behind a whole leaf launch and the merges' lead.
+template <int NF, int TPW>
+__global__ __launch_bounds__(64 * (NF + 1)) void k_leaf_root_gain(LSweepArgs lp, SweepArgs mp, SweepArgs sp, GStreamArgs gp, int nl, int nm) {
+    const int b = (int)blockIdx.x;
+    if (b < nl) lsweep_body<NF, 4, LS_RS4, false, true>(lp, b);
+    else if (b < nl + nm) sweep_body<NF, 1, false, true>(mp, b - nl);
+    else if (b == nl + nm) sweep_body<NF, 1, false, true>(sp, 0);
+    else gain_stream_body<NF + 1, NF, TPW>(gp, b - nl - nm - 1);
 }
 
 // The same pairing for the ring-buffered sweeps (N > 37 clones or tracks of 11 - 15 slots): k_wsweep's fold wavefronts store

@@ -35,6 +35,12 @@ struct LSweepArgs {
     double* rbuf;
     int wide;                   // this launch takes the nodes with w + 1 > 64 (1) or <= 64 (0); the others exit at once
     long long zero_idx;         // index (scalars) of a zero word behind the last block: absent entries load it (no branches)
+    int ld64;                   // output rows of 64 doubles (narrow leaves whose rows are streamed, SweepFold::ld); 0: w + 1
+    // lsweep_body<.., FL = true> (the leaves inside k_leaf_root_gain's launch): a flusher wavefront writes the rows as they become
+    // final and publishes their count in blocks of 8 at progress[FoldNode::pad], (epoch << 32) | rows
+    unsigned long long* progress;
+    unsigned epoch;
+    long long* tstamp;          // optional: [32] wall clock when leaf workgroup 0 starts (the launch head)
 };
 
 constexpr int LS_MAXF = 256;    // features per leaf node
@@ -57,8 +63,9 @@ __host__ __device__ inline size_t lsweep_lds_bytes(int nf) {
            (size_t)nf * G::RB * (4 + 4 + 16);
 }
 
-template <int NF, int CS, int RSLOTS, bool PREF_ = (CS == 4)>
-__global__ __launch_bounds__(64 * NF) void k_lsweep(LSweepArgs p) {
+// FL: one more wavefront, the flusher (k_leaf_root_gain): the leaf's rows leave as they become final instead of at its end
+template <int NF, int CS, int RSLOTS, bool PREF_, bool FL>
+__device__ __forceinline__ void lsweep_body(const LSweepArgs& p, const int bidx) {
     using G = LSweepGeom<CS, RSLOTS>;
     constexpr int W = G::W, RB = G::RB;
     constexpr int CL = 16;
@@ -71,10 +78,13 @@ __global__ __launch_bounds__(64 * NF) void k_lsweep(LSweepArgs p) {
     constexpr int RGAP = PREF ? 1 : NF;             // macro steps between two rounds of a fold slot beyond the w of the fold itself
     constexpr int KGMIN = 1;                        // first chunk whose instance may hold the gathered next block beside the tile
     static_assert(CS >= 4 && CS <= 6, "column slots 4..6");
+    static_assert(!FL || (CS == 4 && !PREF_), "the flusher rides with the 60-column tile without the prefetch (register budget)");
+    constexpr int NT = 64 * (NF + (FL ? 1 : 0));
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    const FoldNode nd = p.nodes[p.node_base + blockIdx.x];
+    const FoldNode nd = p.nodes[p.node_base + bidx];
     if ((nd.w + 1 > 64 ? 1 : 0) != p.wide) return;
     const int t = threadIdx.x;
+    if (FL && p.tstamp && bidx == 0 && t == 0) p.tstamp[32] = wall_clock64();
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int lane = t & 63;
     const int rq = lane >> 4, cq = lane & 15;
@@ -91,11 +101,11 @@ __global__ __launch_bounds__(64 * NF) void k_lsweep(LSweepArgs p) {
     int* rowM = s_nblk + 2 + NF * RB + wv * RB;                // per wave: [RB] views of the row's feature (0: no row)
     unsigned char* rowcols = reinterpret_cast<unsigned char*>(s_nblk + 2 + 2 * NF * RB) + wv * RB * 16;   // per wave: [RB][16]
     double* out = p.rbuf + nd.out_off;
-    const int ldo = w + 1;
+    const int ldo = (p.ld64 && w + 1 <= 64) ? 64 : w + 1;
 
-    for (int e = t; e < (w + 1) * W; e += 64 * NF) smem[e] = 0.0;
+    for (int e = t; e < (w + 1) * W; e += NT) smem[e] = 0.0;
     if (t < 2) smem[zero_i + t] = 0.0;
-    for (int i = t; i < nfeat; i += 64 * NF) {
+    for (int i = t; i < nfeat; i += NT) {
         const int f = nd.src_begin + i;
         qrow[i + 1] = (p.accepted[f] == 1) ? 2 * p.info[f].M - p.rank[f] : 0;
     }
@@ -122,6 +132,63 @@ __global__ __launch_bounds__(64 * NF) void k_lsweep(LSweepArgs p) {
     const int nblk = __builtin_amdgcn_readfirstlane(s_nblk[0]);
     const int nsteps = nblk > 0 ? 1 + ((nblk - 1) / NF) * (w + RGAP) + ((nblk - 1) % NF) + w : 0;
     const int KL = (w - 1) / 8;                                 // last chunk of a fold
+
+    if constexpr (FL) {
+        // The flusher (k_sweep.h's, on the leaf's own schedule): row c is final once the LAST block has run column c, i.e. at
+        // the head of macro step t0(nblk - 1) + c + 1 -- the block count comes from the gate results, which only the device has,
+        // so the schedule is the closed form the fold wavefronts follow.  Rows go out with write-through stores (rows of 64
+        // doubles: ld64), their count three steps later behind a counted vmcnt wait, in blocks of 8 (what a merge fold fetches
+        // per chunk).  It joins the fold wavefronts' barriers bare.
+        if (wv == NF) {
+            const int t0l = nblk > 0 ? 1 + ((nblk - 1) / NF) * (w + RGAP) + ((nblk - 1) % NF) : 0;
+            const unsigned long long ep = (unsigned long long)p.epoch << 32;
+            auto* progw = (__attribute__((address_space(1))) unsigned long long*)(p.progress + nd.pad);
+            int c1 = 0, c2 = 0, l1 = 0, l2 = 0, l3 = 0, published = 0, done = 0;
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();           // (the fold wavefronts' barrier in front of their first gather)
+            asm volatile("" ::: "memory");
+            for (int ts = 0; ts <= nsteps; ++ts) {
+                const int fin = nblk > 0 ? min(max(ts - t0l, 0), w) : w;
+                const int n = fin - done;
+                for (int c = done; c < fin; ++c) {
+                    const double x = Rb[(size_t)c * W + lane];
+                    const int col = (lane == 63) ? w : c + lane;
+                    if (lane == 63 || col < w)
+                        __hip_atomic_store((__attribute__((address_space(1))) unsigned long long*)(unsigned long long*)(out + (size_t)c * ldo + col),
+                                           (unsigned long long)__double_as_longlong(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                done = fin;
+                int issued = n;
+                if ((l3 >> 3) > (published >> 3)) {
+                    // the stores of rows < l3 were issued three steps ago or earlier: c2 + c1 + n instructions since
+                    const int m = c2 + c1 + n;
+                    switch (m < 7 ? m : 7) {
+                        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+                        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+                        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+                        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+                        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+                        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+                        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+                        default: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+                    }
+                    if (lane == 0) __hip_atomic_store(progw, ep | (unsigned)l3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    published = l3;
+                    ++issued;
+                }
+                l3 = l2; l2 = l1; l1 = fin;
+                c2 = c1; c1 = issued;
+                if (ts < nsteps) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                }
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (lane == 0) __hip_atomic_store(progw, ep | (unsigned)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+    }
 
     double a[RSLOTS][CS];
     double nxt[PREF ? RSLOTS : 1][PREF ? CS : 1];
@@ -302,14 +369,20 @@ __global__ __launch_bounds__(64 * NF) void k_lsweep(LSweepArgs p) {
         b = bn;
     }
     while (tcur < nsteps) { __syncthreads(); ++tcur; }
+    if constexpr (FL) return;                              // (the flusher has written the rows)
 
-    // ---- flush R: row-major w x (w+1), entries at and right of the diagonal ----
+    // ---- flush R: row-major w x (w+1) (or rows of ldo), entries at and right of the diagonal ----
     __syncthreads();
     for (int c = wv; c < w; c += NF) {
         const double* Rrow = Rb + (size_t)c * W;
         for (int col = c + lane; col < w; col += 64) out[(size_t)c * ldo + col] = Rrow[col - c];
         if (lane == 0) out[(size_t)c * ldo + w] = Rrow[W - 1];
     }
+}
+
+template <int NF, int CS, int RSLOTS, bool PREF_ = (CS == 4)>
+__global__ __launch_bounds__(64 * NF) void k_lsweep(LSweepArgs p) {
+    lsweep_body<NF, CS, RSLOTS, PREF_, false>(p, (int)blockIdx.x);
 }
 
 }  // namespace msckf

@@ -64,6 +64,8 @@ struct SweepNode {
     int nsteps;                 // macro steps
     long long out_off;          // output block in rbuf: row-major wtot x (wtot+1), or wtot x ldo
     int ldo;                    // doubles per row of the output block (0: wtot + 1)
+    int prod_base;              // streamed sources: SweepFold::prod counts from progress word src_progress[prod_base]
+    int n_gate;                 // ... the step-0 requirements behind this node's own gate table (SweepArgs::gate_per_node)
     int pad;
 };
 
@@ -90,6 +92,8 @@ struct SweepArgs {
     // behind the nsteps + 1 flush entries of the node's table (host: sweep_gate_table): nsteps + 2 step entries (what must be
     // published before macro step t starts: up to two requirements prod << 6 | rows, 12 bits each) | n_gate requirements of step 0
     int n_gate;
+    int gate_per_node;          // the nodes of the launch are consumers with gate tables of their own (k_leaf_root_gain's merge
+                                // workgroups, gated on the leaves): SweepNode::n_gate replaces n_gate, SweepNode::prod_base applies
 };
 
 constexpr int SWEEP_MAX_W = 60;        // widest source / envelope (local column 63 holds the rhs)
@@ -207,7 +211,8 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& p, const int bidx) {
     if constexpr (FL) {
         // (the flusher reads its table from LDS: a vector-memory load per step would make it wait for its own stores)
         const int* tab = p.flush_tab + (p.flush_off ? p.flush_off[bidx] : 0);
-        const int ntab = nsteps + 1 + (p.src_progress ? nsteps + 2 + p.n_gate : 0);
+        const int ngate = p.gate_per_node ? nd.n_gate : p.n_gate;
+        const int ntab = nsteps + 1 + (p.src_progress ? nsteps + 2 + ngate : 0);
         for (int e = t; e < ntab; e += NT) ftab[e] = tab[e];
     }
     // the node's first triangle (t0 == 0) is adopted: its rows ARE the first rows of R, nothing to eliminate
@@ -249,7 +254,9 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& p, const int bidx) {
             // when a requirement is not covered by it -- while the producers are still running the sweep has to wait for them
             // anyway, and once they are through ONE refresh covers every later requirement.  Per step at most two requirements
             // (prod << 6 | rows, 12 bits each: the host moves a third to an earlier step), read with the step's flush entry.
-            const bool gated = p.n_gate >= 0 && p.src_progress;
+            const int ngate = p.gate_per_node ? nd.n_gate : p.n_gate;
+            const bool gated = ngate >= 0 && p.src_progress;
+            const unsigned long long* srcp = p.src_progress + nd.prod_base;
             const int* gtab = ftab + nsteps + 1;            // [nsteps + 2]: entry t = what must be published before macro step t starts
             const int* g0 = gtab + nsteps + 2;              // [n_gate]: ... before the first fetch (step 0)
             int seen_rows = 0;
@@ -260,7 +267,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& p, const int bidx) {
                 while (__builtin_amdgcn_readlane(seen_rows, prod) < rows) {
                     if (tstart == 0) tstart = wall_clock64();
                     else { __builtin_amdgcn_s_sleep(1); if (wall_clock64() - tstart > SWEEP_TIMEOUT_TICKS) { dead = true; break; } }
-                    const unsigned long long v = (lane < p.n_prod) ? __hip_atomic_load((__attribute__((address_space(1))) unsigned long long*)(unsigned long long*)(p.src_progress + lane),
+                    const unsigned long long v = (lane < p.n_prod) ? __hip_atomic_load((__attribute__((address_space(1))) unsigned long long*)(unsigned long long*)(srcp + lane),
                                                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
                     seen_rows = ((unsigned)(v >> 32) == p.epoch) ? (int)(unsigned)v : 0;
                 }
@@ -269,9 +276,10 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& p, const int bidx) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();           // R zeroed / adopted, table in place
             asm volatile("" ::: "memory");
-            if (gated) for (int k = 0; k < p.n_gate && !dead; ++k) need(__builtin_amdgcn_readfirstlane(g0[k]));   // the rows the fold slots fetch before their first step
+            if (gated) for (int k = 0; k < ngate && !dead; ++k) need(__builtin_amdgcn_readfirstlane(g0[k]));   // the rows the fold slots fetch before their first step
             __builtin_amdgcn_s_barrier();           // (the fold wavefronts' second barrier in front of their first fetch)
             asm volatile("" ::: "memory");
+            if (p.tstamp && lane == 0) p.tstamp[33] = wall_clock64();     // (the fold slots start)
             for (int ts = 0; ts <= nsteps; ++ts) {
                 const int e = __builtin_amdgcn_readfirstlane(ftab[ts]);
                 const int ge = gated ? __builtin_amdgcn_readfirstlane(gtab[ts + 1]) : 0;     // (what the folds fetch at the head of the next step)

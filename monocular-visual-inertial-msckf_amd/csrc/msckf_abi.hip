@@ -78,6 +78,11 @@ constexpr int LDS_MAX_BYTES = 160 * 1024;        // gfx950: 160 KiB per workgrou
 #ifndef MSCKF_SWEEP_WPF
 #define MSCKF_SWEEP_WPF 1
 #endif
+// progress words (dMProg) of k_leaf_root_gain: [0, 64) the root's producers (merge nodes, then single-leaf groups), leaf j at
+// LEAF_PROG_BASE + j (the merge nodes poll eight words from their first leaf's on: slack behind the last)
+constexpr int LEAF_PROG_BASE = 64;
+constexpr int LEAF_FUSED_MAX = 256;               // leaves of one fused launch
+constexpr int LEAF_PROG_WORDS = LEAF_PROG_BASE + LEAF_FUSED_MAX + 64;
 constexpr int LS_BIG_BATCH = 4000;               // from this many features on the 60-column leaves run twelve row blocks at a time
 constexpr bool SWEEP_P2P = false;                // (round 2 measured progress words instead of the barrier per macro step: 159 vs 148 us at the root)
 constexpr int SWEEP_NW = MSCKF_SWEEP_NW;         // concurrent folds of k_sweep
@@ -442,8 +447,14 @@ struct msckf_ctx {
     int mflush_at = 0;                    // where h_mflush sits in the uploaded h_root_flush
     bool x_streamed = false; int x_root_n_gate = -1, x_mflush_at = 0;   // the same for rank 0's merge plan (run_merge_groups)
     int root_n_gate = -1;                 // step-0 requirements behind the root's flush + gate tables (sweep_gate_table), -1: no gate table
-    Buf dMFlush, dMProg;                  // ... on the device; the merge nodes' progress words (64)
+    Buf dMFlush, dMProg;                  // ... on the device; the merge nodes' progress words (64), then the fused leaves' (LEAF_PROG_BASE)
     bool stream_enabled = true;           // MSCKF_ROOT_STREAM=0: the level keeps its own launch
+    // The leaves in the same launch as well (k_leaf_root_gain): their rows streamed to the merge nodes (one merge level, 60-column
+    // leaves of eight fold slots, no split long tracks)
+    bool leaf_stream_enabled = true;      // MSCKF_LEAF_STREAM=0: the leaves keep their own launch (A/B)
+    bool leaf_fused = false;              // this plan's merge level and root name the leaves as producers (SweepFold::prod)
+    bool leaf_ld64 = false;               // the leaves' output rows are 64 doubles (streamable)
+    bool leaves_fused_last = false;       // the last pipeline ran k_leaf_root_gain
     int n_cu = 256;                       // compute units of the device: workgroups that wait for each other inside one launch must all be resident
     bool feat_busy = false, pose_busy = false;   // hFeat / hPose may still be read by a copy or by k_gather
     bool main_busy = false;                      // the main stream holds work nobody has waited for
@@ -867,6 +878,12 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
         if (c->cfg.leaf_rows > 0) leaf_feats = 128;
     }
     c->leaf_narrow = c->leaf_wide = false;
+    // leaves that may ride in the root's launch (k_leaf_root_gain): their rows whole cache lines of 64 doubles, 16-double aligned
+    const bool leaf_cand = c->leaf_stream_enabled && c->stream_enabled && mode == 0 && !c->xchg && !c->split_on && runs.size() == 1 &&
+                           6 * max_span + 1 <= 64 && c->leaf_nf == SWEEP_NW && !c->leaf_tall;
+    c->leaf_ld64 = leaf_cand;
+    c->leaf_fused = false;
+    std::vector<int> fold_leaf;                                           // per sweep fold: the leaf node it takes, -1: none
     c->nodes.clear(); c->levels.clear(); c->snodes.clear(); c->sfolds.clear();
     c->sweep_levels.clear(); c->n_group_merges = 0;
     // group exchange: the record [N flags | accepted count | gate bytes (msckf_set_exchange_mask) | N slots of XCHG_SLOT doubles]
@@ -875,7 +892,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
     const bool xchg = c->xchg;
     size_t off = xchg ? rec_head(c) + (size_t)N * XCHG_SLOT + rec_rem_doubles(c) : 0;
     if (xchg) c->h_xflags.assign(N, 0.0);
-    struct Tri { long long src; int lo, w; int lvl = -1, idx = -1, ld = 0; };     // (lvl, idx): the merge node that writes it, if one does; ld: its row stride (0: w + 1)
+    struct Tri { long long src; int lo, w; int lvl = -1, idx = -1, ld = 0, leaf = -1; };   // (lvl, idx): the merge node that writes it, if one does; ld: its row stride (0: w + 1); leaf: the leaf node that does
     const int merge_ld = (c->stream_enabled && mode == 0 && !xchg) ? 64 : 0;      // merge outputs with whole cache lines per row (streamable, k_sweep.h)
     std::vector<Tri> group_tri;                                           // one triangle per group, by first slot
     std::vector<std::vector<SweepNode>> merge_levels;                     // [level] -> nodes of every group at that depth
@@ -911,11 +928,12 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
             FoldNode n{};
             if (xchg) hi = std::min(s + XW / 6, N) - 1;
             n.kind = 0; n.src_begin = f; n.src_end = last + 1; n.win_lo = s; n.w = 6 * (hi - s + 1); n.pad = 0;
+            if (leaf_cand) off = (off + 15) & ~(size_t)15;
             n.out_off = (long long)off;
-            off += (size_t)n.w * (n.w + 1);
+            off += (size_t)n.w * (leaf_cand ? 64 : n.w + 1);
             c->nodes.push_back(n);
             if (n.w + 1 > 64) c->leaf_wide = true; else c->leaf_narrow = true;
-            leaves.push_back({n.out_off, s, n.w});
+            leaves.push_back({n.out_off, s, n.w, -1, -1, leaf_cand ? 64 : 0, (int)c->nodes.size() - 1});
             f = last + 1;
         }
         }
@@ -931,6 +949,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
                 env = std::max(env, cur[i].w);
                 SweepFold sf{}; sf.src_off = cur[i].src; sf.off = 0; sf.w = cur[i].w; sf.ew = env; sf.ld = cur[i].ld;
                 c->sfolds.push_back(sf);
+                fold_leaf.push_back(cur[i].leaf);
                 wtot = std::max(wtot, cur[i].w);
             }
             m.fold_end = (int)c->sfolds.size();
@@ -996,6 +1015,32 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
             group_tri.size() > 1 && 2 * (2 + (dc + 15) / 16 + (int)merge_levels[last].size()) <= c->n_cu) {
             c->root_streamed = true; c->stream_level = last;
         }
+        // ... and the leaves with it: ONE merge level (its nodes take leaves only), each node's triangles on the eight fold slots of
+        // one round with none adopted (a streamed first triangle is folded), every workgroup of the launch on a CU of its own with
+        // the margin root_gain_ok keeps for the root and the strips
+        if (leaf_cand && c->root_streamed && last == 0 && c->n_leaves <= LEAF_FUSED_MAX) {
+            const auto& lv = c->sweep_levels[0];
+            int singles = 0;
+            for (const Tri& g : group_tri) singles += g.leaf >= 0;
+            bool ok = lv.second + singles <= 64 && c->n_leaves + lv.second + 2 * (2 + (dc + 15) / 16) <= c->n_cu;
+            for (int i = lv.first; i < lv.first + lv.second && ok; ++i) ok = c->snodes[i].fold_end - c->snodes[i].fold_begin <= SWEEP_NW;
+            if (ok) {
+                c->leaf_fused = true;
+                for (int i = lv.first; i < lv.first + lv.second; ++i) {
+                    SweepNode& m = c->snodes[i];
+                    sweep_schedule(c->sfolds, m.fold_begin, m.fold_end, &m.nsteps, SWEEP_NW, false);
+                    const int j0 = fold_leaf[m.fold_begin];
+                    m.prod_base = LEAF_PROG_BASE + j0;
+                    for (int g = m.fold_begin; g < m.fold_end; ++g) {
+                        c->sfolds[g].prod = 1 + fold_leaf[g] - j0;             // (a node's leaves are consecutive nodes)
+                        c->nodes[fold_leaf[g]].pad = LEAF_PROG_BASE + fold_leaf[g];
+                    }
+                }
+                int k = lv.second;
+                for (Tri& g : group_tri)
+                    if (g.leaf >= 0) { c->nodes[g.leaf].pad = k; g.lvl = c->stream_level; g.idx = k++; }   // (the root polls the leaf itself)
+            }
+        }
     }
     if (!group_tri.empty()) {
         SweepNode r{};
@@ -1037,19 +1082,22 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
             const auto& lv = c->sweep_levels[c->stream_level];
             c->h_mflush.assign(lv.second, 0);
             // (nodes with the same folds -- the same number of triangles of the same widths: most of them -- share one table)
-            std::vector<std::pair<std::vector<int>, int>> seen_shapes;
+            // (with the leaves in the launch each table carries the node's gate table and step-0 requirements behind it)
+            std::vector<std::pair<std::vector<int>, std::pair<int, int>>> seen_shapes;
             for (int i = 0; i < lv.second; ++i) {
-                const SweepNode& m = c->snodes[lv.first + i];
+                SweepNode& m = c->snodes[lv.first + i];
                 std::vector<int> shape{m.wtot, m.nsteps};
-                for (int g = m.fold_begin; g < m.fold_end; ++g) { shape.push_back(c->sfolds[g].w); shape.push_back(c->sfolds[g].ew); shape.push_back(c->sfolds[g].t0); shape.push_back(c->sfolds[g].off); }
-                int at = -1;
-                for (const auto& sh : seen_shapes) if (sh.first == shape) { at = sh.second; break; }
+                for (int g = m.fold_begin; g < m.fold_end; ++g) { shape.push_back(c->sfolds[g].w); shape.push_back(c->sfolds[g].ew); shape.push_back(c->sfolds[g].t0); shape.push_back(c->sfolds[g].off); shape.push_back(c->sfolds[g].prod); }
+                int at = -1, ng = -1;
+                for (const auto& sh : seen_shapes) if (sh.first == shape) { at = sh.second.first; ng = sh.second.second; break; }
                 if (at < 0) {
                     at = (int)c->h_mflush.size() - lv.second;
                     sweep_flush_table(c->sfolds, m.fold_begin, m.fold_end, m.nsteps, m.wtot, 1 << 29, c->h_mflush);
-                    seen_shapes.push_back({std::move(shape), at});
+                    if (c->leaf_fused) ng = sweep_gate_table(c->sfolds, m.fold_begin, m.fold_end, m.nsteps, SWEEP_NW, c->h_mflush);
+                    seen_shapes.push_back({std::move(shape), {at, ng}});
                 }
                 c->h_mflush[i] = at;
+                m.n_gate = ng;
             }
             c->mflush_at = (int)c->h_root_flush.size();         // (one upload: the merge nodes' tables ride behind the root's)
             c->h_root_flush.insert(c->h_root_flush.end(), c->h_mflush.begin(), c->h_mflush.end());
@@ -1179,9 +1227,7 @@ int launch_fold_levels(msckf_ctx* c, const std::vector<std::pair<int, int>>& lev
 }
 
 // band plan, level 0: the leaves fold their features' K4 blocks (k_lsweep)
-int launch_leaves_band(msckf_ctx* c, int node_base = 0, int count = -1) {
-    if (count < 0) count = c->n_leaves - node_base;
-    if (count <= 0) return MSCKF_OK;
+LSweepArgs lsweep_args(msckf_ctx* c, int node_base) {
     LSweepArgs a{};
     a.nodes = ptr<FoldNode>(c->dNodes);
     a.node_base = node_base;
@@ -1191,6 +1237,13 @@ int launch_leaves_band(msckf_ctx* c, int node_base = 0, int count = -1) {
     a.accepted = ptr<unsigned char>(c->dAcc);
     a.rbuf = ptr<double>(c->dRbuf);
     a.zero_idx = c->stack_elems;
+    a.ld64 = c->leaf_ld64 ? 1 : 0;
+    return a;
+}
+int launch_leaves_band(msckf_ctx* c, int node_base = 0, int count = -1) {
+    if (count < 0) count = c->n_leaves - node_base;
+    if (count <= 0) return MSCKF_OK;
+    LSweepArgs a = lsweep_args(c, node_base);
     const dim3 grid(count), block(64 * SWEEP_NW);
     if (c->leaf_narrow) {
         a.wide = 0;
@@ -1740,9 +1793,10 @@ bool root_gain_ok(const msckf_ctx* c, int band) {
 }
 // A merge level that rides in the root's launch (k_gstream.h): its nodes, where their flush tables sit on the device
 // ([count offsets | tables]) and the root's step-0 requirement count behind its own tables (sweep_gate_table).
+// leaves: the leaves ride too (k_leaf_root_gain), the merge nodes polling them.
 struct MergeRide { int node_base, count, nf, n_gate; const int* flush; size_t lds; };    // lds: what its largest node asks for
 int launch_root_and_gain(msckf_ctx* c, SweepArgs sa, int wtot, int nsteps, const int* flush_tab, const double* Tblk, int band,
-                         const MergeRide* ride = nullptr) {
+                         const MergeRide* ride = nullptr, bool leaves = false) {
     ++c->gs_epoch;
     sa.flush_tab = flush_tab;
     sa.progress = ptr<unsigned long long>(c->dGsProg);
@@ -1764,11 +1818,25 @@ int launch_root_and_gain(msckf_ctx* c, SweepArgs sa, int wtot, int nsteps, const
         ma.flush_off = ride->flush; ma.flush_tab = ride->flush + nm;
         ma.progress = ptr<unsigned long long>(c->dMProg); ma.prog_stride = 1; ma.pub_shift = 3;
         ma.tstamp = nullptr;
-        sa.src_progress = ptr<unsigned long long>(c->dMProg); sa.n_prod = nm; sa.n_gate = ride->n_gate;
+        // (with the leaves the root polls words [0, 64): the merge nodes, then the single-leaf groups)
+        sa.src_progress = ptr<unsigned long long>(c->dMProg); sa.n_prod = leaves ? 64 : nm; sa.n_gate = ride->n_gate;
         lds = std::max(lds, sweep_lds_bytes_fl(wtot, SWEEP_NW, nsteps, ride->n_gate));
         mid = ride->nf == SWEEP_NW_MID;
         lds = std::max(lds, ride->lds);
     }
+    if (leaves && ride && !mid) {
+        ma.src_progress = ptr<unsigned long long>(c->dMProg); ma.n_prod = SWEEP_NW; ma.gate_per_node = 1;
+        LSweepArgs la = lsweep_args(c, 0);
+        la.wide = 0;
+        la.progress = ptr<unsigned long long>(c->dMProg); la.epoch = c->gs_epoch; la.tstamp = sa.tstamp;
+        lds = std::max(lds, lsweep_lds_bytes<4, LS_RS4>(SWEEP_NW));
+        hipLaunchKernelGGL((k_leaf_root_gain<SWEEP_NW, 2>), dim3(c->n_leaves + nm + 1 + ga.ns), dim3(64 * (SWEEP_NW + 1)), lds, c->stream,
+                           la, ma, sa, ga, c->n_leaves, nm);
+        HIPCHK(c, hipGetLastError());
+        c->gain_blocked = false;
+        return MSCKF_OK;
+    }
+    if (leaves) { c->last_error = "k_leaf_root_gain: the plan has no merge level for the leaves"; return MSCKF_ERR_STATE; }
     if (mid) hipLaunchKernelGGL((k_root_gain_m<SWEEP_NW, SWEEP_NW_MID, 2>), dim3(1 + ga.ns + nm), dim3(64 * (SWEEP_NW_MID + 1)), lds, c->stream, sa, ga, ma);
     else hipLaunchKernelGGL((k_root_gain<SWEEP_NW, 2>), dim3(1 + ga.ns + nm), dim3(64 * (SWEEP_NW + 1)), lds, c->stream, sa, ga, ma);
     HIPCHK(c, hipGetLastError());
@@ -1855,7 +1923,11 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     const bool early = c->F > 0 && c->wide_on_stream2 && c->band_plan && c->n_leaves0 > 0 && c->n_leaves0 < c->n_leaves;
     if (early && (rc = launch_leaves_band(c, 0, c->n_leaves0)) != MSCKF_OK) return rc;          // (the short tracks' leaves need not wait)
     if (c->F > 0 && c->wide_on_stream2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_wfeat, 0));
-    if (c->F > 0 && c->band_plan && (rc = launch_leaves_band(c, early ? c->n_leaves0 : 0)) != MSCKF_OK) return rc;
+    // the leaves inside the root's launch (k_leaf_root_gain): a plan made for it (no split long tracks) whose root runs beside K6-K7
+    const bool fuse_leaves = c->F > 0 && c->band_plan && c->leaf_fused && with_gain && c->root >= 0 && c->sweep_mode == 0 &&
+                             gstream_ok(c, c->root_band) && !c->h_root_flush.empty() && root_gain_ok(c, c->root_band);
+    c->leaves_fused_last = fuse_leaves;
+    if (c->F > 0 && c->band_plan && !fuse_leaves && (rc = launch_leaves_band(c, early ? c->n_leaves0 : 0)) != MSCKF_OK) return rc;
     if (c->F > 0 && !c->band_plan && (rc = launch_fold_levels(c, c->levels, c->nodes)) != MSCKF_OK) return rc;
     // (a rank that exports its group triangles stops in front of the root sweep: rank 0 runs it over all shards)
     // K6-K7 beside the root sweep: the band plan's k_sweep root with the flusher wavefront and the update's strips in ONE launch
@@ -1881,6 +1953,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     const bool beside = gs && c->band_plan && c->root >= 0 && !(c->t2_early && t2_split) &&
                         (c->sweep_mode == 0 ? (!c->h_root_flush.empty() && root_gain_ok(c, c->root_band)) : root_gain_w_ok(c, c->root_band));
     const bool streamed = beside && c->sweep_mode == 0 && c->root_streamed;     // the last merge level rides in the root's launch
+    if (fuse_leaves && !streamed) { c->last_error = "k_leaf_root_gain: the root does not run beside K6-K7"; return MSCKF_ERR_STATE; }
     if (c->F > 0 && c->band_plan && (rc = launch_sweeps(c, (with_gain || !c->xchg_planned) && !beside, streamed ? c->stream_level : -1)) != MSCKF_OK) return rc;
     if (c->F > 0 && c->xchg_planned && !with_gain) {       // the accepted count rides in the export record (double N)
         // (with msckf_set_exchange_mask the shard's gate bytes ride behind it, in input order)
@@ -1912,10 +1985,10 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
             const auto& lv = c->sweep_levels[c->stream_level];
             ride = MergeRide{lv.first, lv.second, c->sweep_level_nf[c->stream_level], c->root_n_gate, ptr<int>(c->dRootFlush) + c->mflush_at, 0};
             for (int i = lv.first; i < lv.first + lv.second; ++i)
-                ride.lds = std::max(ride.lds, sweep_lds_bytes_fl(c->snodes[i].wtot, ride.nf, c->snodes[i].nsteps));
+                ride.lds = std::max(ride.lds, sweep_lds_bytes_fl(c->snodes[i].wtot, ride.nf, c->snodes[i].nsteps, fuse_leaves ? c->snodes[i].n_gate : -1));
         }
         if ((rc = launch_root_and_gain(c, a, c->snodes.back().wtot, c->snodes.back().nsteps, ptr<int>(c->dRootFlush), root_block(c),
-                                       c->root_band, streamed ? &ride : nullptr)) != MSCKF_OK) return rc;
+                                       c->root_band, streamed ? &ride : nullptr, fuse_leaves)) != MSCKF_OK) return rc;
         if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[2], c->stream));
     } else {
         if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[2], c->stream));
@@ -2011,6 +2084,7 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     CK(hipEventCreateWithFlags(&c->ev_gate, hipEventDisableTiming), "hipEventCreate");
     if (const char* e = std::getenv("MSCKF_DIRECT_RESULT")) c->direct_enabled = std::atoi(e) != 0;
     if (const char* e = std::getenv("MSCKF_ROOT_STREAM")) c->stream_enabled = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MSCKF_LEAF_STREAM")) c->leaf_stream_enabled = std::atoi(e) != 0;
     auto lds_attr = [&](const void* f, int bytes, const char* what) {
         CK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), what);
     };
@@ -2038,6 +2112,7 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     lds_attr(reinterpret_cast<const void*>(&k_sweep<SWEEP_NW_BIG, 1>), FOLD_LDS_BYTES, "k_sweep<12> LDS attribute");
     lds_attr(reinterpret_cast<const void*>(&k_root_gain<SWEEP_NW, 2>), LDS_MAX_BYTES - 1024, "k_root_gain LDS attribute");
     lds_attr(reinterpret_cast<const void*>(&k_root_gain_m<SWEEP_NW, SWEEP_NW_MID, 2>), LDS_MAX_BYTES - 1024, "k_root_gain_m LDS attribute");
+    lds_attr(reinterpret_cast<const void*>(&k_leaf_root_gain<SWEEP_NW, 2>), LDS_MAX_BYTES - 1024, "k_leaf_root_gain LDS attribute");
     lds_attr(reinterpret_cast<const void*>(&k_root_gain_w<SWEEP_NW, 4, 2>), LDS_MAX_BYTES - 1024, "k_root_gain_w LDS attribute");
     lds_attr(reinterpret_cast<const void*>(&k_root_gain_w<SWEEP_NW, 4, 3>), LDS_MAX_BYTES - 1024, "k_root_gain_w LDS attribute");
     lds_attr(reinterpret_cast<const void*>(&k_root_gain_w<SWEEP_NW, 6, 2>), LDS_MAX_BYTES - 1024, "k_root_gain_w LDS attribute");
@@ -2098,8 +2173,8 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
         E(c->dGsEx, (nbm + GS_MAX_NB2) * nsm * 256 * 8);      // (two sources of row blocks: the band root and the remainder rows of split long tracks)
         E(c->dRem, 16 * (size_t)GS_MAX_NB2 * (dc + 1) * 8 + 64);   // the dense remainder rows (k_rem_scatter) + their count
         E(c->dGsFlag, ((nbm + GS_MAX_NB2) * nsm + 8) * 8, true);
-        E(c->dMProg, 512, true);                       // (progress words of the merge workgroups inside k_root_gain's launch)
-        E(c->dGsProg, 512, true);                      // (progress word at 0, k_root_gain's time stamps on a line of their own at byte 256)
+        E(c->dMProg, LEAF_PROG_WORDS * 8, true);       // (progress words of the merge / leaf workgroups inside k_root_gain's launch)
+        E(c->dGsProg, 1024, true);                     // (progress word at 0, k_root_gain's time stamps on a line of their own at byte 256)
     }
     if (rc != MSCKF_OK) { msckf_destroy(c); return rc; }
     {
@@ -2695,13 +2770,16 @@ int msckf_run_timed(msckf_ctx* c, int32_t iters, float* ms_total, float* stage_u
                 long long ts[3] = {0, 0, 0};
                 HIPCHK(c, hipMemcpy(ts, ptr<long long>(c->dGsProg) + 32, 24, hipMemcpyDeviceToHost));
                 if (std::getenv("MSCKF_GS_DEBUG")) {
-                    long long t8[32];
-                    HIPCHK(c, hipMemcpy(t8, ptr<long long>(c->dGsProg) + 32, 256, hipMemcpyDeviceToHost));
+                    long long t8[34];
+                    HIPCHK(c, hipMemcpy(t8, ptr<long long>(c->dGsProg) + 32, sizeof(t8), hipMemcpyDeviceToHost));
                     std::fprintf(stderr, "k_root_gain (us after the sweep started): last row published %.1f, update done %.1f | strip 0 saw the row blocks at",
                                  (t8[1] - t8[0]) * 0.01, (t8[2] - t8[0]) * 0.01);
                     for (int b = 0; b < (c->dc + 15) / 16 && b < 15; ++b) std::fprintf(stderr, " %.1f", (t8[3 + b] - t8[0]) * 0.01);
                     std::fprintf(stderr, " | the flusher published them at");
                     for (int b = 1; b < (c->dc + 15) / 16 && b < 14; ++b) std::fprintf(stderr, " %.1f", (t8[18 + b] - t8[0]) * 0.01);
+                    if (c->leaves_fused_last)
+                        std::fprintf(stderr, " | launch head -> root's first step %.1f us, -> last row %.1f, -> update done %.1f",
+                                     (t8[33] - t8[32]) * 0.01, (t8[1] - t8[32]) * 0.01, (t8[2] - t8[32]) * 0.01);
                     std::fprintf(stderr, "\n");
                 }
                 const double tail = (double)(ts[2] - ts[1]) * 0.01;
@@ -2793,7 +2871,8 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
         st->stacked_rows = counters[1]; st->not_spd = counters[2];
         st->n_leaves = c->n_leaves;
         st->n_levels = (int)c->levels.size() + (c->band_plan ? (int)c->sweep_levels.size() + 1 : 0);
-        st->k5_launches = st->n_levels - ((c->band_plan && c->gs_fused_last && c->sweep_mode == 0 && c->root_streamed) ? 1 : 0);   // (a streamed merge level rides in the root's launch)
+        st->k5_launches = st->n_levels - ((c->band_plan && c->gs_fused_last && c->sweep_mode == 0 && c->root_streamed) ? 1 : 0)   // (a streamed merge level rides in the root's launch)
+                          - ((c->band_plan && c->gs_fused_last && c->leaves_fused_last) ? 1 : 0);                                  // (... and the leaves with it)
         st->us_total = c->us_total; st->us_feature = c->us_stage[0]; st->us_qr = c->us_stage[1];
         st->us_gain = c->us_stage[2];
         st->us_host_prep = c->us_host_prep; st->us_h2d = c->us_h2d; st->us_d2h = c->us_d2h;

@@ -1,34 +1,41 @@
 #!/usr/bin/env python3
 """bench.py -- MSCKF measurement-updates/sec on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one complete measurement update (K1..K7: per-feature Jacobian stack,
 nullspace projection, chi-square gate, QR compression, gain, Joseph covariance
 update) of ONE filter over one synthetic feature batch.
+
+A plain run does only what the headline figure needs: it sets up, warms up, times
+the K steps, writes --dump-outputs and prints ONE JSON line with the contract keys
+(`metric`, `value`, `unit`, `ms_per_step`, ...).  Everything else below is measured
+only with --full.
 
 N = 1 : BASELINE.json configs[2] (headline: N=30 clones, 2000 features, track 10,
         fp64).  `value` is the metric BASELINE.md / SURVEY 8(d) define: the complete
         drop-in call (host arrays in -> dx, P+, mask on the host: sort, plan, PCIe both
         ways), K steps over FOUR DIFFERENT batches in rotation (seeds 0..3), so that
         the K5 plan cache misses on every call as it does in a filter that gets new
-        tracks every frame.  `value_resident` is the rate with state, sorted tracks and
-        plan resident in HBM (HIP events over the same number of steps), and
-        `value_host_inclusive_cache_hit` the drop-in call on a repeated batch.  The same
-        line carries one row per other single-GPU config (configs[1], the north-star
-        target (30, 10000, 10), configs[3] on one GPU, configs[4] in fp64 and with fp32
-        storage, a long-span batch, a 10 %-outlier batch) with its own roofline
-        fractions, `roofline` for the dominant kernel group (K5) and `cpu_baseline`.
+        tracks every frame.  With --full: `value_resident` is the rate with state,
+        sorted tracks and plan resident in HBM (HIP events over the same number of
+        steps), and `value_host_inclusive_cache_hit` the drop-in call on a repeated
+        batch.  The same line carries one row per other single-GPU config (configs[1],
+        the north-star target (30, 10000, 10), configs[3] on one GPU, configs[4] in fp64
+        and with fp32 storage, a long-span batch, a 10 %-outlier batch) with its own
+        roofline fractions, `roofline` for the dominant kernel group (K5) and
+        `cpu_baseline`.
 N > 1 : (launched by torch.distributed.run, one rank per GPU; only RANK / LOCAL_RANK /
         WORLD_SIZE are read -- the exchange is librccl behind the C-ABI, no PyTorch)
         the feature-sharded update of BASELINE.json configs[3]: `value` = updates/s of
         the 8000-feature update split over the N ranks ("scaling": "strong"), ONE RCCL
         gather of the compressed group records to rank 0, serial gain there, ONE RCCL
-        broadcast of status | dx | P+ | gate bytes; the weak-scaling figure (2000
-        features per rank) rides in the same line.
+        broadcast of status | dx | P+ | gate bytes.  With --full the same update
+        unsharded on one GPU and the weak-scaling figure (2000 features per rank) ride
+        in the same line.
 
 Rank 0 prints ONE JSON line.  The oracle (oracle/msckf_oracle.py) is only timed
-as the CPU baseline; it is never on the measured GPU path.
+as the CPU baseline (--full); it is never on the measured GPU path.
 
 --dump-outputs DIR: rank 0 writes what the timed path returned on its last timed
 step (status, dx, P_new, accepted; the strong case at N > 1) as DIR/<name>.npy in
@@ -238,9 +245,13 @@ def main():
     ap.add_argument("--clones", type=int, default=30)
     ap.add_argument("--features", type=int, default=2000, help="features per GPU")
     ap.add_argument("--track", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="headline only (profiling runs)")
-    ap.add_argument("--no-mode-i-headline", action="store_true", help="skip the one-minute dense-eye CPU baseline at the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: resident rate, stage times, rooflines, the other configs, "
+                         "f1-f4 and the CPU baseline at one GPU; the unsharded run and weak scaling at N > 1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full: no other configs (profiling runs)")
+    ap.add_argument("--no-mode-i-headline", action="store_true",
+                    help="with --full: skip the one-minute dense-eye CPU baseline at the headline")
     ap.add_argument("--force-dist", action="store_true", help="run the sharded code path even at world size 1")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the result of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
@@ -256,7 +267,7 @@ def main():
 
     use_dist = world > 1 or args.force_dist
     import msckf_amd  # noqa: F401
-    from msckf_amd import synth, _ffi
+    from msckf_amd import synth
     from msckf_amd.api import UpdateEngine
 
     if use_dist:
@@ -280,11 +291,6 @@ def main():
         call_s = (time.perf_counter() - t0) / args.steps
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, last.status, last.dx, last.P_new, last.accepted)
-    prob, res, one, head, costs = time_config(N, Fg, M, args.steps, args.warmup, device=local_rank, host_reps=20)
-    stats = one.stats
-    us_step = head["us_per_update"]
-    us_qr = head["stages_us"]["qr_K5"]
-    n_lv = max(1, head["k5_launches"])
     line = {
         "metric": "MSCKF measurement-updates/sec (N=30 clones, 2000 features, track=10)",
         "value": 1.0 / call_s,
@@ -302,8 +308,28 @@ def main():
                    "unit_definition": "one 2000-feature measurement update (K1-K7)", "seeds": [0, 1, 2, 3],
                    "value_definition": "the metric of BASELINE.md / SURVEY 8(d): the complete drop-in call, host arrays in -> dx, P+, "
                                        "mask on the host (sort, plan, PCIe both ways, K1-K7), `steps` calls over four different "
-                                       "batches in rotation so that the K5 plan cache misses on every call; value_resident = K1-K7 "
-                                       "with state, sorted tracks and plan resident in HBM, HIP events over `steps` pipelines"},
+                                       "batches in rotation so that the K5 plan cache misses on every call"},
+    }
+    if args.full:
+        full_single_gpu(args, line, call_s, local_rank)
+    else:
+        print(json.dumps(line), flush=True)
+
+
+def full_single_gpu(args, line, call_s, local_rank):
+    """--full at one GPU: everything beside the headline figure, measured after its timed steps and added to `line`, which
+    emit() prints (the detail goes to bench_detail.json)."""
+    from msckf_amd import synth, _ffi
+    from msckf_amd.api import UpdateEngine
+    N, Fg, M = args.clones, args.features, args.track
+    prob, res, one, head, costs = time_config(N, Fg, M, args.steps, args.warmup, device=local_rank, host_reps=20)
+    stats = one.stats
+    us_step = head["us_per_update"]
+    us_qr = head["stages_us"]["qr_K5"]
+    n_lv = max(1, head["k5_launches"])
+    line["config"]["value_definition"] += ("; value_resident = K1-K7 with state, sorted tracks and plan resident in HBM, HIP events "
+                                           "over `steps` pipelines")
+    line.update({
         "value_resident": head["updates_per_s"],
         "ms_per_step_resident": us_step * 1e-3,
         "value_host_inclusive_cache_hit": head["host_inclusive_cache_hit_updates_per_s"],
@@ -311,7 +337,7 @@ def main():
         "host_inclusive_breakdown_us": {"call": call_s * 1e6, "call_cache_hit": head["host_inclusive_cache_hit_us"],
                                         "device_pipeline": us_step,
                                         "host_sort_plan": head["host_prep_us"], "h2d": head["h2d_us"], "d2h": head["d2h_us"]},
-    }
+    })
     k5_names = ("k_lsweep<", "k_sweep<", "k_wsweep<", "k_root_gain<", "k_root_gain_m<")
     ex = pmc_executed_flops(k5_names)
     line["roofline"] = {
@@ -577,8 +603,9 @@ def emit(detail):
 
 def bench_sharded(args, world, rank, local_rank):
     """N > 1: one rank per GPU, exchange on librccl behind the C-ABI (msckf_comm_*, no PyTorch).  `value` is
-    BASELINE.json configs[3] as written -- ONE 8000-feature update split over the ranks ("strong") --; the weak
-    figure (2000 features per rank, counted as 2000-feature update equivalents) rides in the same line."""
+    BASELINE.json configs[3] as written -- ONE 8000-feature update split over the ranks ("strong") --.  With --full the
+    unsharded run on rank 0 and the weak figure (2000 features per rank, counted as 2000-feature update equivalents) ride
+    in the same line."""
     from msckf_amd import synth
     from msckf_amd.api import UpdateEngine
     from msckf_amd.shard import RcclShardedUpdate, exchange_unique_id
@@ -632,7 +659,7 @@ def bench_sharded(args, world, rank, local_rank):
     # the same 8000-feature update on ONE GPU (rank 0's, unsharded, resident in HBM): what the strong-scaling figure is a
     # speed-up over.  The other ranks wait in the bootstrap of the first sharded case.
     one_gpu_us = None
-    if rank == 0:
+    if rank == 0 and args.full:
         p8 = synth.make_problem(N, 8000, M, seed=0)
         with UpdateEngine(max_clones=N, max_features=8000, max_track=max(M, 2), device=local_rank) as e1:
             e1.load(p8)
@@ -644,8 +671,9 @@ def bench_sharded(args, world, rank, local_rank):
     s_seconds, s_groups, st2, s_acc, s_rej, s_out = run_case(8000, args.steps, args.warmup, "_strong")
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, st2, *s_out)
-    weak_steps = max(10, min(args.steps, 100))
-    seconds, groups, st1, _, _, _ = run_case(Fg * world, weak_steps, min(args.warmup, 10), "_weak")
+    if args.full:
+        weak_steps = max(10, min(args.steps, 100))
+        seconds, groups, st1, _, _, _ = run_case(Fg * world, weak_steps, min(args.warmup, 10), "_weak")
     line = None
     if rank == 0:
         line = {
@@ -666,8 +694,12 @@ def bench_sharded(args, world, rank, local_rank):
                                    "no PyTorch); shards resident in HBM",
                        "exchange": "group triangles" if s_groups else "root blocks",
                        "unit_definition": "one 8000-feature measurement update (K1-K7)", "seed": 0},
-            "status": [int(st2), int(st1)],
+            "status": [int(st2)],                            # one per case run: strong, then weak with --full
             "accepted": s_acc, "rejected": s_rej,
+        }
+    if rank == 0 and args.full:
+        line["status"].append(int(st1))
+        line.update({
             "one_gpu_same_workload": {"us_per_update": one_gpu_us, "updates_per_s": 1e6 / one_gpu_us,
                                       "what": "the unsharded 8000-feature update on rank 0's GPU, resident in HBM (HIP events)"},
             "speedup_vs_one_gpu": (args.steps / s_seconds) / (1e6 / one_gpu_us),
@@ -677,7 +709,7 @@ def bench_sharded(args, world, rank, local_rank):
                 "update_equivalents_per_s": weak_steps * world / seconds,
                 "unit_definition": "update_equivalents = 2000-feature updates' worth of features per second",
                 "steps": weak_steps, "exchange": "group triangles" if groups else "root blocks", "scaling": "weak"},
-        }
+        })
     return line
 
 

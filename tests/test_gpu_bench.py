@@ -1,10 +1,12 @@
 """bench.py's multi-GPU leg, exercised before a driver ever runs it on an 8-GPU node: the sharded code path at world
 size 1 (`--force-dist`: id file, stdout kept for the ONE JSON line, strong + weak cases, the one-GPU reference run) in
-a fresh interpreter, and the default one-GPU line's shape."""
+a fresh interpreter, and the default one-GPU line's shape; a plain run (no --full) of each, which measures the headline
+only."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -28,7 +30,7 @@ def _run_bench(extra, timeout=600, max_len=None):
 
 
 def test_sharded_leg_at_world_one():
-    j = _run_bench(["--force-dist", "--steps", "3", "--warmup", "1"], max_len=4096)
+    j = _run_bench(["--force-dist", "--full", "--steps", "3", "--warmup", "1"], max_len=4096)
     assert j["status"] == [0, 0]
     assert j["scaling"] == "strong" and j["n_gpus"] == 1
     assert j["accepted"] + j["rejected"] == 8000
@@ -38,12 +40,44 @@ def test_sharded_leg_at_world_one():
     assert j["config"]["exchange"] == "group triangles"
 
 
-def test_the_drivers_command_prints_one_short_line():
-    """The command the driver runs at round end, no extra flags: ONE stdout line under 4 KB (round 4's 20 KB line came back
-    unparsed) with `roofline` and `cpu_baseline`; the detail lands in bench_detail.json."""
+def test_plain_sharded_leg_at_world_one():
+    """Without --full the sharded leg times the strong case alone: no unsharded run, no weak case."""
+    j = _run_bench(["--force-dist", "--steps", "3", "--warmup", "1"], max_len=4096)
+    assert j["status"] == [0]
+    assert j["scaling"] == "strong" and j["n_gpus"] == 1 and j["steps"] == 3
+    assert j["accepted"] + j["rejected"] == 8000
+    assert j["value"] > 0 and j["ms_per_step"] > 0
+    assert "weak_scaling" not in j and "one_gpu_same_workload" not in j
+    assert j["config"]["exchange"] == "group triangles"
+
+
+def test_the_drivers_command_prints_the_headline_only():
+    """The command the driver runs, no extra flags: ONE stdout line with the contract keys and nothing that needs runs of its
+    own; no bench_detail.json; at most 30 s of the whole run outside its warm-up and timed steps."""
+    detail = os.path.join(ROOT, "bench_detail.json")
+    before = os.stat(detail).st_mtime_ns if os.path.exists(detail) else None
+    t0 = time.perf_counter()
+    j = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=300, max_len=4096)
+    wall = time.perf_counter() - t0
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config"):
+        assert key in j, key
+    assert j["steps"] == 20 and j["warmup"] == 5 and j["n_gpus"] == 1
+    assert j["unit"] == "updates/s" and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert j["value"] > 0 and abs(j["value"] * j["ms_per_step"] - 1e3) < 1e-3
+    for key in ("value_resident", "roofline", "cpu_baseline", "north_star_roofline", "stages_us"):
+        assert key not in j, key
+    assert (os.stat(detail).st_mtime_ns if os.path.exists(detail) else None) == before
+    outside = wall - (20 + 5) * j["ms_per_step"] * 1e-3
+    assert outside < 30.0, outside
+
+
+def test_the_full_run_prints_one_short_line():
+    """--full at the driver's sizes: ONE stdout line under 4 KB (round 4's 20 KB line came back unparsed) with `roofline` and
+    `cpu_baseline`; the detail lands in bench_detail.json."""
     env = dict(os.environ)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], cwd=ROOT,
-                         env=env, capture_output=True, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
+                         cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0]) < 4096, (len(lines), [len(l) for l in lines])
@@ -64,7 +98,7 @@ def test_the_drivers_command_prints_one_short_line():
 
 
 def test_one_gpu_line_shape():
-    j = _run_bench(["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extra-configs"])
+    j = _run_bench(["--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extra-configs"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in j, key
@@ -81,7 +115,7 @@ def test_dump_outputs_are_the_last_timed_step(tmp_path):
     from msckf_amd import synth
     from oracle import msckf_oracle as oracle
     out = tmp_path / "dump"
-    j = _run_bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-configs", "--dump-outputs", str(out)])
+    j = _run_bench(["--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
     assert j["steps"] == 3
     got = {n: np.load(str(out / (n + ".npy"))) for n in ("status", "dx", "accepted", "P_new")}
     assert all(a.dtype == np.float64 for a in got.values())

@@ -15,7 +15,7 @@ cd "$ROOT"
 if [ $# -ge 3 ]; then
   CMD="python3 tools/one_config.py $*"
 else
-  CMD="python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs"
+  CMD="python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs"
 fi
 echo "$CMD" > $out/command.txt
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- $CMD > $out/stats_bench.log 2>&1 &&

@@ -77,7 +77,7 @@ typedef struct msckf_ctx msckf_ctx;
 typedef struct msckf_config {
     int32_t abi_version;            /* MSCKF_ABI_VERSION                                    */
     int32_t device;                 /* HIP device ordinal                                   */
-    int32_t max_clones;             /* capacity: N                                          */
+    int32_t max_clones;             /* capacity: N  (<= 221, else MSCKF_ERR_ARG)            */
     int32_t max_features;           /* capacity: F                                          */
     int32_t max_track;              /* capacity: M  (<= MSCKF_MAX_TRACK)                    */
     int32_t leaf_rows;              /* 0 = default; target stacked rows per QR leaf         */

@@ -367,6 +367,7 @@ struct msckf_ctx {
     int root_band = 0;                    // widest row of the root block in columns (the local plan's / the merge plan's)
     bool gs_stamp = false;                // msckf_run_timed: k_root_gain notes when its sweep ends and when its update ends
     bool gs_fused_last = false;           // the last pipeline ran k_root_gain (stage events cannot split it)
+    bool gs_last = false;                 // the last pipeline's K6-K7 was k_gain_stream (fused or a launch of its own)
     // tracks that span more than WIDE_SPAN clone slots are sorted behind the others ([0, Fb) short, [Fb, F) long) and split
     int Fb = 0, Fw = 0, Fw1 = 0, Mmax_band = 0, Mmax_wide = 0, Mmax_w1 = 0;   // (Fw1 of the Fw wide tracks have <= 15 views)
     // Round 5: a long track (more than WIDE_SPAN clone slots) is SPLIT (k_feature.h, two-level nullspace basis): the sorted
@@ -1217,9 +1218,16 @@ int launch_fold_levels(msckf_ctx* c, const std::vector<std::pair<int, int>>& lev
             }
 #undef FOLD_LAUNCH
         } else {                                // wide windows: R streamed through HBM
+            // (k_fold_g<T, RPT, CPT> holds CPT * T / 16 columns, the rhs included: an instance narrower than the node would
+            //  drop its last columns.  Fewer rows per batch as the columns grow; the widest window, dc + 1 = 1327, takes 42 per
+            //  lane.  Speed at these widths is not measured.)
             const dim3 block(FOLDG_T);
-            if (maxw + 1 <= 6 * 32) hipLaunchKernelGGL((k_fold_g<FOLDG_T, 12, 6>), grid, block, FOLD_LDS_BYTES, st, a);
-            else hipLaunchKernelGGL((k_fold_g<FOLDG_T, 6, 10>), grid, block, FOLD_LDS_BYTES, st, a);
+            constexpr int NCG = FOLDG_T / 16;
+            if (maxw + 1 <= 6 * NCG) hipLaunchKernelGGL((k_fold_g<FOLDG_T, 12, 6>), grid, block, FOLD_LDS_BYTES, st, a);
+            else if (maxw + 1 <= 10 * NCG) hipLaunchKernelGGL((k_fold_g<FOLDG_T, 6, 10>), grid, block, FOLD_LDS_BYTES, st, a);
+            else if (maxw + 1 <= 21 * NCG) hipLaunchKernelGGL((k_fold_g<FOLDG_T, 2, 21>), grid, block, FOLD_LDS_BYTES, st, a);
+            else if (maxw + 1 <= 42 * NCG) hipLaunchKernelGGL((k_fold_g<FOLDG_T, 1, 42>), grid, block, FOLD_LDS_BYTES, st, a);
+            else { c->last_error = "k_fold_g: a merge node is wider than its widest instance"; return MSCKF_ERR_STATE; }
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -1541,6 +1549,22 @@ int launch_chol_solve_blocked(msckf_ctx* c, double* S, const double* Y, double* 
     return MSCKF_OK;
 }
 
+// K = Y S^-1 for windows past the LDS solve: k_solve<NR> holds, solves and stores 64 NR columns, so the instance taken is the
+// smallest NR >= nreg = ceil(dc / 64).  SOLVE_MAX_NREG covers the widest window msckf_create accepts (N = 221, dc = 1326: 21);
+// a wider dc is refused, never solved on its first 64 SOLVE_MAX_NREG columns.
+constexpr int SOLVE_MAX_NREG = 21;
+template <int NR>
+int launch_solve_regs(msckf_ctx* c, int nreg, const SolveArgs& a) {
+    if constexpr (NR < SOLVE_MAX_NREG) {
+        if (nreg > NR) return launch_solve_regs<NR + 1>(c, nreg, a);
+    } else if (nreg > NR) {
+        c->last_error = "K6-K7: the window is wider than k_solve covers";
+        return MSCKF_ERR_STATE;
+    }
+    hipLaunchKernelGGL(k_solve<NR>, dim3(a.d), dim3(64), 0, c->stream, a);
+    return MSCKF_OK;
+}
+
 // K6-K7 from the root block [T | r_n] (dc x (dc+1), row-major) and the prior P.
 int launch_gain(msckf_ctx* c, const double* Tblk) {
     const int d = c->d, dc = c->dc, ldt = dc + 1;
@@ -1593,8 +1617,7 @@ int launch_gain(msckf_ctx* c, const double* Tblk) {
                 if (nreg <= 1) SOLVE_LAUNCH(1, false); else if (nreg <= 2) SOLVE_LAUNCH(2, false); else SOLVE_LAUNCH(3, false);
             }
 #undef SOLVE_LAUNCH
-        } else if (nreg <= 4) hipLaunchKernelGGL(k_solve<4>, dim3(d), dim3(64), 0, c->stream, a);
-        else hipLaunchKernelGGL(k_solve<5>, dim3(d), dim3(64), 0, c->stream, a);
+        } else if (int rcs = launch_solve_regs<4>(c, nreg, a)) return rcs;
     }
     }
     if (c->cfg.dtype == MSCKF_DTYPE_F32) {
@@ -1964,6 +1987,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     }
     if (c->t2_early && c->wide_on_stream2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));     // (its P_out / dx are what the update below starts from)
     c->gs_fused_last = beside;
+    c->gs_last = gs;
     if (beside && c->sweep_mode > 0) {
         const SweepNode& rn = c->snodes.back();
         const double* zero = ptr<double>(c->dRbuf) + c->zero_off;
@@ -2098,6 +2122,8 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     }
     lds_attr(reinterpret_cast<const void*>(&k_fold_g<FOLDG_T, 12, 6>), FOLD_LDS_BYTES, "k_fold_g LDS attribute");
     lds_attr(reinterpret_cast<const void*>(&k_fold_g<FOLDG_T, 6, 10>), FOLD_LDS_BYTES, "k_fold_g LDS attribute");
+    lds_attr(reinterpret_cast<const void*>(&k_fold_g<FOLDG_T, 2, 21>), FOLD_LDS_BYTES, "k_fold_g LDS attribute");
+    lds_attr(reinterpret_cast<const void*>(&k_fold_g<FOLDG_T, 1, 42>), FOLD_LDS_BYTES, "k_fold_g LDS attribute");
     {
 #define SK(NR, UN) reinterpret_cast<const void*>(&k_solve_lds<NR, SOLVE_WAVES, SOLVE_ROWS, UN>)
         const void* sk[] = {SK(1, true), SK(2, true), SK(3, true), SK(1, false), SK(2, false), SK(3, false)};
@@ -2824,9 +2850,10 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
         c->last_error = "K6-K7 did not report a status";
         rc = MSCKF_ERR_HIP;
     }
-    {   // MSCKF_DEBUG_FAKE_TIMEOUT=1 (tests): the first update of a context reads as timed out
+    {   // MSCKF_DEBUG_FAKE_TIMEOUT=1 (tests): the first streamed update of a context reads as timed out (fused with the root sweep
+        // up to 53 clones; a k_gain_stream launch of its own at 54 - 82, whose workgroups wait for each other all the same)
         static const bool fake = [] { const char* e = std::getenv("MSCKF_DEBUG_FAKE_TIMEOUT"); return e && std::atoi(e) == 1; }();
-        if (fake && !c->fake_timeout_done && rc == MSCKF_OK && c->ran_gain && c->gs_fused_last) { c->fake_timeout_done = true; status[0] = 2; rc = MSCKF_ERR_NOT_SPD; }
+        if (fake && !c->fake_timeout_done && rc == MSCKF_OK && c->ran_gain && c->gs_last) { c->fake_timeout_done = true; status[0] = 2; rc = MSCKF_ERR_NOT_SPD; }
     }
     if (rc == MSCKF_ERR_NOT_SPD && (status[0] == 2 || (c->x_status1 && status[1] == 2))) {       // k_gain_stream gave up waiting for rows of T or for another workgroup
         // The workgroups of k_root_gain / k_gain_stream wait for each other inside their launch; that they are all resident is

@@ -882,8 +882,9 @@ def test_gate_statistic_of_long_tracks(M):
 
 @pytest.mark.parametrize("N", list(range(1, 54)))
 def test_every_window_size(eng, N):
-    """One small batch per window size 1 - 53 against the oracle: every strip count of K6-K7, every length of its short first
-    row block (6 N mod 16), the sweep forms on either side of N = 37 and the wide-track rule on either side of N = 31."""
+    """One small batch per window size 1 - 53 against the oracle: strip counts 2 - 21 of the streamed K6-K7, every length of its
+    short first row block (6 N mod 16), the sweep forms on either side of N = 37 and the wide-track rule on either side of N = 31.
+    Windows of 54 clones and more: tests/test_gpu_wide_windows.py."""
     from msckf_amd import synth
     from oracle import msckf_oracle as oracle
     M = max(1, min(N, 2 + N % 9))

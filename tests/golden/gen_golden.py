@@ -13,6 +13,7 @@ Only numeric arrays are written -- no reference source or bytecode.
 
     python tests/golden/gen_golden.py            # all cases except the 45 s headline
     python tests/golden/gen_golden.py --headline # also cfg3 (needs ~12 GB RAM, ~1 min)
+    python tests/golden/gen_golden.py --window30 # only the 30-clone filter run, window30/seq_window30.npz
 """
 import argparse
 import copy
@@ -46,7 +47,7 @@ from src.msckf.MSCKF import MSCKF, MSCKFParameters  # noqa: E402
 from src.msckf.Camera import Camera  # noqa: E402
 from src.msckf.FeatureExtractor import Feature  # noqa: E402
 from src.msckf.IMU import IMUMeasurement  # noqa: E402
-from src.utils.geometry import Isometry3D, InverseDepthPoint, Line  # noqa: E402
+from src.utils.geometry import Isometry3D, InverseDepthPoint, Line, angle_between_directions, intersection_of_lines  # noqa: E402
 
 import scipy  # noqa: E402
 from scipy.stats import chi2  # noqa: E402
@@ -362,6 +363,415 @@ def run_reference_sequence(seed, frames=6, imu_per_frame=8, F=40, M=5, max_clone
     return arrays
 
 
+W30_KINDS = dict(imu=0, augment=1, process=2, prune=3, remove=4)
+
+
+def run_reference_window30(seed=7, frames=45, imu_per_frame=4, active=110, probe_cols=2, min_lost=2):
+    """A 30-clone filter run of the reference's own MSCKF object in the order of `feature_callback`
+    (`MSCKF.py:147-158`): per frame process_imu x imu_per_frame, state_augmentation, the new views appended as
+    `add_camera_measurements` does (`:403-434`, matcher bypassed), the reference's own `process_features()`
+    (`:450-456`) and `prune_poorest_camera_states()` (`:710-737`) once more than 30 clones are held.
+
+    Persistent synthetic landmarks (tracks of 2 - 35 frames, a few landmarks with outlier views); lines and inverse-depth
+    points are built as the reference builds them, so their bases ARE the clones' position arrays (`geometry.py:26, 55`)
+    and move with every injection (`:661`).  Returns (arrays, stats).  Op kinds: W30_KINDS."""
+    rng = np.random.default_rng(31000 + seed)
+    params = MSCKFParameters()
+    # a feature missed in one frame stays in the window (:463-465): its track gets a hole, and a clone few features saw
+    # can be the poorest one while newer and older clones hold more (with gap-free tracks the count per clone grows
+    # with its age, and the prune would always take the two oldest)
+    params.min_number_of_frames_to_be_lost = min_lost
+    f = MSCKF(params)
+    imu = f.state.imu
+    imu.is_initialized = True
+    f.first_measurement_arrived = True
+    imu.v_W_Ii = np.array([1.5, 0.2, 0.0])
+    imu.v_W_Ii_null = np.array([1.5, 0.2, 0.0])
+    imu.gyroscope_bias = 1e-3 * rng.standard_normal(3)
+    imu.accelerometer_bias = 1e-2 * rng.standard_normal(3)
+    f.state.covariance = np.diag([1e-4] * 3 + [1e-6] * 3 + [1e-3] * 3 + [1e-5] * 3 + [1e-3] * 3).astype(float)
+    Kf = np.asarray(f.K, dtype=np.float64)
+    V = rng.standard_normal((15 + 6 * 31, probe_cols))
+    out = dict(P0=f.state.covariance.copy(), Qc=f.continuous_noise_covariance.copy(),
+               T_W_I_R=imu.T_W_I.R.copy(), T_W_I_t=imu.T_W_I.t.copy(),
+               T_W_C_R=np.array(f.T_W_C.R, dtype=float), T_W_C_t=np.array(f.T_W_C.t, dtype=float),
+               gravity=np.array(imu.W_gravity, dtype=float), K=Kf.copy(), sigma=np.float64(f.sigma_image), V=V,
+               select_params=np.array([f.min_number_of_frames_to_be_lost, f.min_number_of_frames_to_be_tracked,
+                                       int(f.use_parallax), f.min_parallax, f.width, f.height], dtype=np.float64),
+               max_clones=np.int32(f.max_number_of_camera_states))
+    R = {k: [] for k in ("op_kind", "op_index", "imu", "aug", "probe", "probe_op", "ckpt", "ckpt_op")}
+    pool = {k: [] for k in ("uv", "dir", "score", "key", "lid")}
+    pool_of = {}                        # (feature id, clone key) -> pool index
+    calls = []
+    margins = dict(gate=np.inf, parallax=np.inf, project=np.inf)
+    ctx = {}
+
+    def op(kind, index):
+        R["op_kind"].append(kind)
+        R["op_index"].append(index)
+
+    def probe(skip=False):
+        if skip:
+            return
+        P = f.state.covariance
+        R["probe"].append(P @ V[:P.shape[0]])
+        R["probe_op"].append(len(R["op_kind"]) - 1)
+
+    def checkpoint():
+        P = f.state.covariance
+        R["ckpt"].append(P[np.triu_indices(P.shape[0])])
+        R["ckpt_op"].append(len(R["op_kind"]) - 1)
+
+    # -- capture: integrate (per IMU sample), get_valid_features / gating_test / correct / remove_cameras (per call) ----
+    snap = {}
+    orig_integrate = imu.integrate
+
+    def integrate(linear_acceleration, angular_velocity, dt):
+        orig_integrate(linear_acceleration=linear_acceleration, angular_velocity=angular_velocity, dt=dt)
+        snap.update(acc=np.array(linear_acceleration), gyro=np.array(angular_velocity), dt=np.float64(dt),
+                    R=imu.T_W_Ii.R.copy(), t=imu.T_W_Ii.t.copy(), v=imu.v_W_Ii.copy(),
+                    R0=imu.T_W_Ii_null.R.copy(), t0=imu.T_W_Ii_null.t.copy(), v0=imu.v_W_Ii_null.copy(),
+                    w_planet=np.array(imu.planet_angular_velocity, dtype=float))
+    imu.integrate = integrate
+
+    orig_gvf, orig_gate, orig_correct, orig_rmc = f.get_valid_features, f.gating_test, f.correct, f.remove_cameras
+
+    def get_valid_features(features):
+        cams = f.state.cameras
+        keys = list(cams.keys())
+        for k in keys:
+            assert cams[k].T_W_Ci_null is cams[k].T_W_Ci                        # Camera.py:10-11: null follows current
+        bases, base_idx = [], {}
+
+        def base_row(arr):
+            key = id(arr)
+            if key not in base_idx:
+                base_idx[key] = len(bases)
+                bases.append(np.array(arr, dtype=np.float64))
+            return base_idx[key]
+        for k in keys:
+            base_row(cams[k].T_W_Ci.t)
+        c = dict(kind=ctx["kind"], frame=ctx["frame"], keys=np.array(keys, dtype=np.int32),
+                 ids=[], lost=[], tracked=[], nview=[], pool=[], vbase=[], ibase=[], m=[], rho=[])
+        for fid, ft in features.items():
+            for kp, ci, ln in zip(ft.keypoints, ft.camera_indices, ft.lines):
+                assert ln.base is cams[ci].T_W_Ci.t                               # the view's line rides its clone (:410)
+                c["pool"].append(pool_of[(fid, ci)])
+                c["vbase"].append(base_row(ln.base))
+            idp = ft.inverse_depth_point
+            c["ids"].append(fid)
+            c["lost"].append(ft.lost_for_n_frames)
+            c["tracked"].append(ft.tracked_for_n_frames)
+            c["nview"].append(len(ft.keypoints))
+            c["ibase"].append(base_row(idp.base))
+            c["m"].append(np.array(idp.m, dtype=np.float64))
+            c["rho"].append(float(idp.rho))
+            # distance of every selection decision from its threshold (:464-484, Camera.py:18-26)
+            lost = ft.lost_for_n_frames >= f.min_number_of_frames_to_be_lost
+            if lost and ft.tracked_for_n_frames < f.min_number_of_frames_to_be_tracked:
+                continue
+            enough = False
+            if f.use_parallax and len(ft.lines) > 1:
+                par = np.rad2deg(angle_between_directions(ft.lines[0].direction, ft.lines[-1].direction))
+                margins["parallax"] = min(margins["parallax"], abs(par - f.min_parallax) / f.min_parallax)
+                enough = par > f.min_parallax
+            if lost or enough:
+                W_p, _ = intersection_of_lines(ft.lines)
+                cam = cams[ft.camera_indices[0]]
+                Cp = cam.W2Ci(W_p)
+                margins["project"] = min(margins["project"], abs(Cp[2]) / np.linalg.norm(Cp))
+                if Cp[2] > 0:
+                    im = (Kf @ Cp)[:2] / (Kf @ Cp)[2]
+                    for x, hi in ((im[0], f.width), (im[1], f.height)):
+                        margins["project"] = min(margins["project"], abs(x) / hi, abs(x - hi) / hi)
+        c["bases"] = np.array(bases).reshape(-1, 3)
+        n_world = len(f.estimated_world_points)
+        touched = []
+        orig_update = InverseDepthPoint.update
+
+        def idp_update(self_, depth, direction):                                # :488
+            touched.append(id(self_))
+            return orig_update(self_, depth, direction)
+        InverseDepthPoint.update = idp_update
+        try:
+            valid, lostd = orig_gvf(features)
+        finally:
+            InverseDepthPoint.update = orig_update
+        flags = []
+        for fid, ft in features.items():
+            flags.append((1 if fid in valid else 0) | (2 if fid in lostd else 0))
+        new_m = np.stack([np.asarray(ft.inverse_depth_point.m, dtype=np.float64) for ft in features.values()]) if features else np.zeros((0, 3))
+        new_rho = np.array([float(ft.inverse_depth_point.rho) for ft in features.values()])
+        m0, rho0 = np.array(c["m"]).reshape(-1, 3), np.array(c["rho"])
+        refreshed = [j for j, ft in enumerate(features.values()) if id(ft.inverse_depth_point) in touched]
+        assert len(refreshed) == len(f.estimated_world_points) - n_world
+        for j in refreshed:
+            flags[j] |= 4
+        c.update(flags=np.array(flags, dtype=np.uint8), ref_m=new_m[refreshed], ref_rho=new_rho[refreshed],
+                 ref_world=np.array(f.estimated_world_points[n_world:]).reshape(-1, 3),
+                 valid_ids=list(valid.keys()), gate=[], status=1, dx=None, rm=[])
+        calls.append(c)
+        ctx["call"] = c
+        return valid, lostd
+
+    def gating_test(r, H):
+        passed = orig_gate(r, H)
+        S = H @ f.state.covariance @ H.T + f.sigma_image ** 2 * np.eye(H.shape[0])
+        gamma = float((r.T @ np.linalg.inv(S) @ r).flatten()[0])
+        crit = float(chi2.ppf(0.95, r.shape[0]))
+        assert passed == (gamma <= crit)
+        margins["gate"] = min(margins["gate"], abs(gamma - crit) / crit)
+        ctx["call"]["gate"].append(1 if passed else 0)
+        ctx["call"]["rows"] = ctx["call"].get("rows", 0) + (r.shape[0] if passed else 0)
+        return passed
+
+    def correct(Kg, T_H, R_n, delta_x):
+        ctx["call"]["dx"] = np.array(delta_x).flatten()
+        ctx["call"]["status"] = 0
+        ctx["call"]["qr"] = int(ctx["call"]["rows"] > T_H.shape[1])                # :594
+        return orig_correct(Kg, T_H, R_n, delta_x)
+
+    def finish_process():
+        c = ctx["call"]
+        keys = list(f.state.cameras.keys())
+        c["post_R"] = np.stack([f.state.cameras[k].T_W_Ci.R for k in keys])
+        c["post_t"] = np.stack([f.state.cameras[k].T_W_Ci.t for k in keys])
+        op(W30_KINDS["process"], len(calls) - 1)
+        probe()
+        ctx["post_done"] = True
+
+    def remove_cameras(cameras):
+        keys = list(f.state.cameras.keys())
+        slots = sorted(keys.index(k) for k in cameras)
+        if ctx["kind"] == W30_KINDS["process"] and slots:
+            finish_process()                            # the tail of remove_features (:749) is an op of its own
+        orig_rmc(cameras)
+        if slots:
+            ctx["call"]["rm"] = slots
+            if ctx["kind"] == W30_KINDS["process"]:
+                op(W30_KINDS["remove"], len(calls) - 1)
+                probe()
+
+    f.get_valid_features, f.gating_test, f.correct, f.remove_cameras = get_valid_features, gating_test, correct, remove_cameras
+
+    # -- landmarks ---------------------------------------------------------------------------------------------------
+    Kinv = np.linalg.inv(Kf)
+    lm = {}                                    # landmark id -> dict(p, last frame, outlier rate, feature id)
+    n_lm = [0]
+
+    def spawn(frame, cam):
+        u, v = rng.uniform(40, 600), rng.uniform(40, 440)
+        near = rng.uniform() < 0.3
+        depth = rng.uniform(1.2, 3.0) if near else rng.uniform(3.0, 12.0)
+        p = cam.T_W_Ci.R @ (Kinv @ np.array([u, v, 1.0]) * depth) + cam.T_W_Ci.t
+        r = rng.uniform()
+        life = int(rng.integers(2, 9)) if r < 0.4 else int(rng.integers(9, 21)) if r < 0.75 else int(rng.integers(21, 36))
+        lm[n_lm[0]] = dict(p=p, last=frame + life - 1, out=0.5 if rng.uniform() < 0.12 else 0.0, fid=None)
+        n_lm[0] += 1
+
+    def observe(L, cam):
+        q = cam.T_W_Ci.R.T @ (L["p"] - cam.T_W_Ci.t)
+        if q[2] < 0.3:
+            return None
+        uv = (Kf @ q)[:2] / q[2] + 0.4 * rng.standard_normal(2)
+        if rng.uniform() < L["out"]:
+            a = rng.uniform(0, 2 * np.pi)
+            uv = uv + rng.uniform(150, 400) * np.array([np.cos(a), np.sin(a)])
+        if not (0 <= uv[0] < 640 and 0 <= uv[1] < 480):
+            return None
+        return np.float32(uv).astype(np.float64)
+
+    def add_view(fid, ft, kp, cam, key, score, lid):
+        W_v = cam.Ci2W(cam.inverse_project_point(kp), is_versor=True)               # :403-404
+        ft.keypoints.append(kp)
+        ft.descriptors.append(np.zeros(1))
+        ft.scores.append(score)
+        ft.camera_indices.append(key)
+        ft.lines.append(Line(cam.T_W_Ci.t, W_v, score))                             # :410 (base = the clone's array)
+        ft.tracked_for_n_frames += 1
+        ft.lost_for_n_frames = 0
+        pool_of[(fid, key)] = len(pool["uv"])
+        for name, val in (("uv", kp), ("dir", W_v), ("score", score), ("key", key), ("lid", lid)):
+            pool[name].append(val)
+        return W_v
+
+    tnow = 0.0
+    n31 = False
+    for frame in range(frames):
+        for s in range(imu_per_frame):
+            tnow += 0.005
+            Rw = imu.T_W_Ii.R
+            a_w = np.array([0.4 * np.cos(1.5 * tnow), 0.6 * np.sin(2.0 * tnow), 0.2 * np.sin(1.1 * tnow)])
+            acc = Rw.T @ (a_w + imu.W_gravity) + 1e-3 * rng.standard_normal(3)
+            gyro = np.array([0.05 * np.sin(tnow), 0.04 * np.cos(0.7 * tnow), 0.1 * np.sin(0.5 * tnow)]) + 1e-4 * rng.standard_normal(3)
+            f.process_imu(IMUMeasurement(tnow, gyro, acc))
+            R["imu"].append(dict(snap))
+            op(W30_KINDS["imu"], len(R["imu"]) - 1)
+            probe(skip=s < imu_per_frame - 1)
+        imu_R, imu_t = imu.T_W_Ii.R.copy(), imu.T_W_Ii.t.copy()
+        f.state_augmentation()
+        key = f.state.imu.id
+        cam = f.state.cameras[key]
+        R["aug"].append(dict(imu_R=imu_R, imu_t=imu_t, cam_R=cam.T_W_Ci.R.copy(), cam_t=cam.T_W_Ci.t.copy(), key=key))
+        op(W30_KINDS["augment"], len(R["aug"]) - 1)
+        probe()
+        if len(f.state.cameras) == 31 and not n31:
+            checkpoint()
+            n31 = True
+        # -- add_camera_measurements, matcher bypassed (:403-434) -------------------------------------------------------
+        alive = [i for i, L in lm.items() if L["last"] >= frame]
+        while len(alive) < active:
+            spawn(frame, cam)
+            alive.append(n_lm[0] - 1)
+        seen = set()
+        p_miss = 0.45 if frame % 6 == 3 and frame > 6 else 0.05                # now and then a frame that loses many
+        for i in alive:
+            L = lm[i]
+            fid = L["fid"]
+            if fid in f.features and f.features[fid].lost_for_n_frames == 0 and L["last"] > frame and rng.uniform() < p_miss:
+                continue                                                        # missed once: a hole in the track
+            kp = observe(L, cam)
+            if kp is None:
+                L["last"] = frame - 1
+                continue
+            score = float(np.float32(rng.uniform(0.5, 1.0)))
+            if L["fid"] is None or L["fid"] not in f.features:
+                if L["fid"] is not None:
+                    continue                                                    # its feature is gone: the landmark too
+                f.last_feature_index += 1
+                fid = f.last_feature_index
+                ft = Feature()
+                W_v = add_view(fid, ft, kp, cam, key, score, i)
+                ft.inverse_depth_point = InverseDepthPoint(cam.T_W_Ci, W_v)     # :431 (base = the clone's array)
+                f.features[fid] = ft
+                L["fid"] = fid
+            else:
+                add_view(L["fid"], f.features[L["fid"]], kp, cam, key, score, i)
+            seen.add(L["fid"])
+        for fid, ft in f.features.items():
+            if fid not in seen:
+                ft.lost_for_n_frames += 1                                           # :438
+        # -- process_features, then the prune (:155-158) ---------------------------------------------------------------
+        ctx.update(kind=W30_KINDS["process"], frame=frame, post_done=False, call=None)
+        n_calls = len(calls)
+        f.process_features()
+        assert len(calls) == n_calls + 1
+        c = calls[-1]
+        if not ctx["post_done"]:
+            finish_process()
+        c["exit_ids"] = list(f.features.keys())
+        c["exit_nview"] = [len(ft.keypoints) for ft in f.features.values()]
+        if len(f.state.cameras) > f.max_number_of_camera_states:
+            ctx.update(kind=W30_KINDS["prune"], frame=frame, call=None)
+            counts = {}
+            for ft in f.features.values():
+                for ci in ft.camera_indices:
+                    counts[ci] = counts.get(ci, 0) + 1
+            f.prune_poorest_camera_states()
+            c = calls[-1]
+            assert c["kind"] == W30_KINDS["prune"] and len(c["rm"]) == 2
+            left = list(f.state.cameras.keys())
+            c["post_R"] = np.stack([f.state.cameras[k].T_W_Ci.R for k in left])
+            c["post_t"] = np.stack([f.state.cameras[k].T_W_Ci.t for k in left])
+            c["counts"] = np.array(list(counts.items()), dtype=np.int32)                  # (key, count) in dict order
+            c["exit_ids"] = list(f.features.keys())
+            c["exit_nview"] = [len(ft.keypoints) for ft in f.features.values()]
+            op(W30_KINDS["prune"], len(calls) - 1)
+            probe()
+    checkpoint()
+
+    # -- flatten -----------------------------------------------------------------------------------------------------
+    out["op_kind"] = np.array(R["op_kind"], dtype=np.int8)
+    out["op_index"] = np.array(R["op_index"], dtype=np.int32)
+    for k in ("acc", "gyro", "dt", "R", "t", "v", "R0", "t0", "v0", "w_planet"):
+        out["imu_" + k] = np.array([s[k] for s in R["imu"]])
+    for k in ("imu_R", "imu_t", "cam_R", "cam_t", "key"):
+        out["aug_" + k] = np.array([a[k] for a in R["aug"]])
+    out["aug_key"] = out["aug_key"].astype(np.int32)
+    out["pool_uv"] = np.array(pool["uv"], dtype=np.float32)
+    assert np.array_equal(out["pool_uv"].astype(np.float64), np.array(pool["uv"]))
+    out["pool_dir"] = np.array(pool["dir"])
+    out["pool_score"] = np.array(pool["score"], dtype=np.float32)
+    out["pool_key"] = np.array(pool["key"], dtype=np.int32)
+    out["pool_lid"] = np.array(pool["lid"], dtype=np.int32)
+
+    def cat(name, dtype=None, shape=None):
+        parts = [np.asarray(c[name], dtype=dtype).reshape((-1,) + (shape or ())) for c in calls]
+        return np.concatenate(parts), np.cumsum([0] + [len(p) for p in parts]).astype(np.int32)
+    out["call_kind"] = np.array([c["kind"] for c in calls], dtype=np.int8)
+    out["call_frame"] = np.array([c["frame"] for c in calls], dtype=np.int32)
+    out["call_status"] = np.array([c["status"] for c in calls], dtype=np.int8)
+    out["call_n_rejected"] = np.array([len(c["gate"]) - sum(c["gate"]) for c in calls], dtype=np.int32)
+    out["call_qr"] = np.array([c.get("qr", -1) for c in calls], dtype=np.int8)
+    out["call_keys"], out["call_kptr"] = cat("keys", np.int32)
+    out["call_ids"], out["call_fptr"] = cat("ids", np.int32)
+    out["call_lost"], _ = cat("lost", np.int16)
+    out["call_tracked"], _ = cat("tracked", np.int16)
+    out["call_nview"], _ = cat("nview", np.int16)
+    out["call_ibase"], _ = cat("ibase", np.int16)
+    # inverse-depth points at entry: a row only where it differs from the same feature's row in the call before
+    last = {}
+    for c in calls:
+        chg = []
+        for fid, m, rho in zip(c["ids"], c["m"], c["rho"]):
+            prev = last.get(fid)
+            chg.append(prev is None or not (np.array_equal(prev[0], m) and prev[1] == rho))
+            last[fid] = (m, rho)
+        c["mchg"] = chg
+        c["m_new"] = [m for m, k in zip(c["m"], chg) if k]
+        c["rho_new"] = [r for r, k in zip(c["rho"], chg) if k]
+    out["call_mchg"], _ = cat("mchg", np.uint8)
+    out["call_m"], _ = cat("m_new", np.float64, (3,))
+    out["call_rho"], _ = cat("rho_new", np.float64)
+    out["call_pool"], out["call_vptr"] = cat("pool", np.int32)
+    out["call_vbase"], _ = cat("vbase", np.int16)
+    out["call_bases"], out["call_bptr"] = cat("bases", np.float64, (3,))
+    out["call_flags"], _ = cat("flags", np.uint8)
+    for c in calls:
+        acc = np.zeros(len(c["ids"]), dtype=np.uint8)
+        vj = [j for j in range(len(c["ids"])) if c["flags"][j] & 1]
+        if c["gate"]:
+            acc[vj] = c["gate"]
+        c["accepted"] = acc
+        c["dx"] = np.zeros(0) if c["dx"] is None else c["dx"]
+        c["rm"] = np.array(c["rm"], dtype=np.int32)
+        c["post_R"] = c.get("post_R", np.zeros((0, 3, 3)))
+        c["post_t"] = c.get("post_t", np.zeros((0, 3)))
+        c["counts"] = c.get("counts", np.zeros((0, 2), dtype=np.int32))
+    out["call_accepted"], _ = cat("accepted", np.uint8)
+    out["call_ref_m"], out["call_rptr"] = cat("ref_m", np.float64, (3,))
+    out["call_ref_rho"], _ = cat("ref_rho", np.float64)
+    out["call_ref_world"], _ = cat("ref_world", np.float64, (3,))
+    out["call_dx"], out["call_dxptr"] = cat("dx", np.float64)
+    out["call_rm"], out["call_rmptr"] = cat("rm", np.int32)
+    out["call_post_R"], out["call_pptr"] = cat("post_R", np.float64, (3, 3))
+    out["call_post_t"], _ = cat("post_t", np.float64, (3,))
+    out["call_counts"], out["call_cptr"] = cat("counts", np.int32, (2,))
+    out["call_exit_ids"], out["call_eptr"] = cat("exit_ids", np.int32)
+    out["call_exit_nview"], _ = cat("exit_nview", np.int16)
+    out["probe"] = np.concatenate(R["probe"])
+    out["probe_op"] = np.array(R["probe_op"], dtype=np.int32)
+    out["ckpt"] = np.concatenate(R["ckpt"])
+    out["ckpt_op"] = np.array(R["ckpt_op"], dtype=np.int32)
+    out["margins"] = np.array([margins["gate"], margins["parallax"], margins["project"]])
+    out["versions"] = np.array([np.__version__, scipy.__version__, sys.version.split()[0]])
+    return out
+
+
+def write_window30(seed=7):
+    """window30/seq_window30.npz: kept out of the top-level globs of tests/conftest.py (its layout is not seq_*'s)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import window30
+    arrays = run_reference_window30(seed)
+    stats = window30.properties(window30.Run(arrays))
+    window30.assert_properties(stats)
+    d = os.path.join(HERE, "window30")
+    os.makedirs(d, exist_ok=True)
+    path = os.path.join(d, "seq_window30.npz")
+    np.savez_compressed(path, **arrays)
+    print(f"seq_window30 size={os.path.getsize(path) / 1024:.0f} KiB", {k: v for k, v in stats.items()}, flush=True)
+
+
 def coincident_clone_problem(seed):
     """SURVEY.md section 7 hard part 4: rank(H_f) < 3.  Clones 0..3 share one position (pure rotation), so a track
     seen only from them has H_f w = 0 for the common ray w: scipy's null_space returns 2M - 2 columns there
@@ -597,7 +1007,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--headline", action="store_true")
     ap.add_argument("--only", default=None)
+    ap.add_argument("--window30", action="store_true", help="only the 30-clone run window30/seq_window30.npz")
     args = ap.parse_args()
+    if args.window30:
+        write_window30()
+        return
 
     cases = {}
     # config 1 and 2, recipe A (random SPD P) and B (P and poses from the reference's own propagation)

@@ -12,7 +12,8 @@
  * (:581-588), QR compression (:594-598), Kalman gain (:604-607) and the
  * Joseph-form covariance update with symmetrisation (:612-614).
  * The state injection half of `correct` (:616-661, N+1 3x3 exp-maps) stays on
- * the host (Python, see monocular-visual-inertial-msckf_amd/api.py).
+ * the host (Python, see monocular-visual-inertial-msckf_amd/api.py) unless the
+ * nominal state is resident too (msckf_set_nominal ... msckf_commit_inject).
  *
  * Conventions
  *   - plain pointers and sizes, row-major, float64 ("double") unless stated;
@@ -255,6 +256,44 @@ int msckf_set_poses(msckf_ctx* ctx, const double* cam_R, const double* cam_t,
                     const double* cam_R0, const double* cam_t0);
 /* Download the resident prior covariance (d x d, d = 15 + 6 N) and N; P may be NULL. */
 int msckf_get_covariance(msckf_ctx* ctx, double* P, int32_t* N);
+
+/* ---- the nominal state resident beside the covariance --------------------- *
+ * With these the filter loop between two msckf_set_features calls needs no host arithmetic and no round trip:
+ *   MSCKF.process_imu (all samples of a frame)  -> msckf_propagate_imu      IMU.integrate + Phi, Q + covariance, one call
+ *   MSCKF.state_augmentation                    -> msckf_augment_imu        clone pose and J from the resident IMU state
+ *   MSCKF.correct                               -> msckf_commit_inject      P <- P+ and the state injection from dx in HBM
+ * msckf_set_nominal uploads the record once (after msckf_set_state, which holds the clone poses); every call below
+ * returns MSCKF_ERR_STATE before it.  The record is fp64 in both dtypes.
+ * The older calls stay legal on such a context: msckf_set_poses (and msckf_set_state) override the clone poses,
+ * msckf_augment appends the pose the caller gives; msckf_propagate and msckf_augment leave the IMU record alone (the
+ * caller who mixes them keeps it consistent); msckf_remove_clones compacts the device arrays instead of re-uploading
+ * the host's copy, which is stale after an injection until msckf_get_nominal refreshes it. */
+typedef struct msckf_nominal {
+    double R[9], t[3], v[3];        /* IMU.T_W_Ii.R / .t, IMU.v_W_Ii                         (IMU.py:27-28)      */
+    double b_g[3], b_a[3];          /* IMU.gyroscope_bias, IMU.accelerometer_bias            (IMU.py:33-34)      */
+    double R0[9], t0[3], v0[3];     /* IMU.T_W_Ii_null, IMU.v_W_Ii_null (IMU.py:38-39).  From the first
+                                       msckf_propagate_imu on they follow the state, injections included: the
+                                       reference holds the same objects for both (MSCKF.py:247-248)              */
+    double gravity[3];              /* IMU.W_gravity                                                             */
+    double planet_rate[3];          /* IMU.planet_angular_velocity                           (IMU.py:36)         */
+    double Qc[144];                 /* continuous_noise_covariance, 12x12 row-major          (MSCKF.py:99-103)   */
+    double T_I_C_R[9], T_I_C_t[3];  /* static extrinsics T_W_I^-1 T_W_C                      (MSCKF.py:252)      */
+} msckf_nominal;
+#define MSCKF_IMU_BATCH_MAX 64      /* samples of one msckf_propagate_imu (they travel in the kernel arguments)  */
+int msckf_set_nominal(msckf_ctx* ctx, const msckf_nominal* s);
+/* Download the record and the clone poses (cam_R N*9, cam_t N*3, nullable; null poses equal them); drains the stream. */
+int msckf_get_nominal(msckf_ctx* ctx, msckf_nominal* s, double* cam_R, double* cam_t);
+/* MSCKF.process_imu (MSCKF.py:160-248) for n consecutive RAW samples, 1 <= n <= MSCKF_IMU_BATCH_MAX (else
+ * MSCKF_ERR_ARG): gyro, acc n*3, dt n.  The biases are subtracted on the device.  Two launches whatever n is (one
+ * before the first clone), asynchronous.  The clone columns see the product of the n transitions, which rounds a few
+ * ulp differently from n calls. */
+int msckf_propagate_imu(msckf_ctx* ctx, int32_t n, const double* gyro, const double* acc, const double* dt);
+/* MSCKF.state_augmentation (MSCKF.py:250-265) from the resident IMU state and T_I_C; asynchronous. */
+int msckf_augment_imu(msckf_ctx* ctx);
+/* msckf_commit_covariance, then MSCKF.correct's state injection (MSCKF.py:616-661) of this update's dx, read from HBM:
+ * IMU state, biases, every clone pose and null pose.  Same return codes; a no-op (1) or failed update (< 0) leaves P
+ * and the record untouched.  Asynchronous wherever msckf_commit_covariance is. */
+int msckf_commit_inject(msckf_ctx* ctx);
 
 /* ---- feature-sharded path (one context per GPU / rank) ------------------ *
  * Each rank holds a shard of the features and the full state.  It runs K1-K5

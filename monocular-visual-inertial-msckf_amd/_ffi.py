@@ -34,6 +34,7 @@ SYMBOLS = [
     "msckf_comm_allreduce", "msckf_comm_buffer", "msckf_comm_put", "msckf_comm_get",
     "msckf_set_exchange_mask", "msckf_result_range_doubles", "msckf_get_shared_result", "msckf_set_exchange_span",
     "msckf_debug_split", "msckf_debug_set_rem_direct_rows", "msckf_exchange_split_rule", "msckf_set_exchange_split",
+    "msckf_set_nominal", "msckf_get_nominal", "msckf_propagate_imu", "msckf_augment_imu", "msckf_commit_inject",
 ]
 
 
@@ -65,6 +66,15 @@ class SelectParamsC(C.Structure):
                 ("min_parallax_deg", C.c_double), ("K", C.c_double * 9)]
 
 
+class NominalC(C.Structure):
+    """msckf_nominal: the nominal state kept beside the covariance (IMU state, null state, constants)."""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("v", C.c_double * 3), ("b_g", C.c_double * 3),
+                ("b_a", C.c_double * 3), ("R0", C.c_double * 9), ("t0", C.c_double * 3), ("v0", C.c_double * 3),
+                ("gravity", C.c_double * 3), ("planet_rate", C.c_double * 3), ("Qc", C.c_double * 144),
+                ("T_I_C_R", C.c_double * 9), ("T_I_C_t", C.c_double * 3)]
+
+
+IMU_BATCH_MAX = 64      # MSCKF_IMU_BATCH_MAX: samples of one msckf_propagate_imu
 SEL_VALID, SEL_LOST, SEL_REFRESHED = 1, 2, 4
 
 _lib = None
@@ -193,6 +203,15 @@ def load():
     lib.msckf_set_poses.restype = C.c_int
     lib.msckf_get_covariance.argtypes = [vp, _dp, _ip]
     lib.msckf_get_covariance.restype = C.c_int
+    lib.msckf_set_nominal.argtypes = [vp, C.POINTER(NominalC)]
+    lib.msckf_set_nominal.restype = C.c_int
+    lib.msckf_get_nominal.argtypes = [vp, C.POINTER(NominalC), _dp, _dp]
+    lib.msckf_get_nominal.restype = C.c_int
+    lib.msckf_propagate_imu.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
+    lib.msckf_propagate_imu.restype = C.c_int
+    for name in ("msckf_augment_imu", "msckf_commit_inject"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = C.c_int
     lib.msckf_debug_split.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.msckf_debug_split.restype = C.c_int
     lib.msckf_debug_set_rem_direct_rows.argtypes = [vp, C.c_int32]

@@ -359,6 +359,62 @@ class UpdateEngine:
         self._check(self._lib.msckf_get_covariance(self._h, _ffi.dptr(P), C.byref(n)), allow_noop=False)
         return P
 
+    # -- the nominal state resident beside the covariance ----------------------
+    def set_nominal(self, R, t, v, gravity, noise, T_W_I=None, T_W_C=None, b_g=None, b_a=None, R0=None, t0=None, v0=None,
+                    planet_rate=None, T_I_C=None):
+        """Upload the IMU state once (after `set_prior` / `set_state`): from here on `propagate_imu`, `augment_imu` and
+        `commit_inject` keep it, the biases and the clone poses on the device.  `noise`: the 12x12 continuous noise
+        covariance (reference `MSCKF.py:99-103`); `T_W_I`, `T_W_C`: (R, t) of the static IMU and camera frames, or
+        `T_I_C` = (R, t) of their composition (`:252`).  Null state: `R0, t0, v0`, default the state itself."""
+        from . import propagation
+        if T_I_C is None:
+            if T_W_I is None or T_W_C is None:
+                raise ValueError("give T_I_C, or T_W_I and T_W_C")
+            T_I_C = propagation.extrinsics(T_W_I, T_W_C)
+        z3 = np.zeros(3)
+        s = _ffi.NominalC()
+        for name, val, size in (("R", R, 9), ("t", t, 3), ("v", v, 3), ("b_g", z3 if b_g is None else b_g, 3),
+                                ("b_a", z3 if b_a is None else b_a, 3), ("R0", R if R0 is None else R0, 9),
+                                ("t0", t if t0 is None else t0, 3), ("v0", v if v0 is None else v0, 3),
+                                ("gravity", gravity, 3), ("planet_rate", z3 if planet_rate is None else planet_rate, 3),
+                                ("Qc", noise, 144), ("T_I_C_R", T_I_C[0], 9), ("T_I_C_t", T_I_C[1], 3)):
+            a = np.asarray(val, dtype=np.float64).reshape(-1)
+            if a.size != size:
+                raise ValueError(f"{name} has {a.size} entries, expected {size}")
+            setattr(s, name, (C.c_double * size)(*a))
+        self._check(self._lib.msckf_set_nominal(self._h, C.byref(s)), allow_noop=False)
+
+    def nominal(self) -> dict:
+        """The nominal state as it stands on the device (waits for the stream): `R, t, v, b_g, b_a, R0, t0, v0` of the
+        IMU and `cam_R` (N, 3, 3), `cam_t` (N, 3) of the clones, whose null poses equal their poses."""
+        s = _ffi.NominalC()
+        N = self._N
+        cam_R, cam_t = np.zeros((max(N, 1), 3, 3)), np.zeros((max(N, 1), 3))
+        self._check(self._lib.msckf_get_nominal(self._h, C.byref(s), _ffi.dptr(cam_R), _ffi.dptr(cam_t)), allow_noop=False)
+        out = {k: np.array(getattr(s, k)) for k in ("t", "v", "b_g", "b_a", "t0", "v0")}
+        out["R"], out["R0"] = np.array(s.R).reshape(3, 3), np.array(s.R0).reshape(3, 3)
+        out["cam_R"], out["cam_t"] = cam_R[:N], cam_t[:N]
+        return out
+
+    def propagate_imu(self, gyro, acc, dt):
+        """`process_imu` (reference `MSCKF.py:160-248`) for up to `_ffi.IMU_BATCH_MAX` consecutive RAW samples in one
+        call: integration, `Phi`, `Q` and the covariance on the device; async."""
+        g, a, t = _ffi.f64(gyro).reshape(-1), _ffi.f64(acc).reshape(-1), _ffi.f64(dt).reshape(-1)
+        if g.size != 3 * t.size or a.size != 3 * t.size:
+            raise ValueError("gyro and acc are (n, 3), dt (n,)")
+        self._check(self._lib.msckf_propagate_imu(self._h, int(t.size), _ffi.dptr(g), _ffi.dptr(a), _ffi.dptr(t)),
+                    allow_noop=False)
+
+    def augment_imu(self):
+        """`state_augmentation` (reference `MSCKF.py:250-265`) from the resident IMU state; async."""
+        self._check(self._lib.msckf_augment_imu(self._h), allow_noop=False)
+        self._N += 1
+        self._F = 0
+
+    def commit_inject(self) -> int:
+        """`commit_covariance` + the state injection of `MSCKF.correct` (reference `MSCKF.py:616-661`) on the device."""
+        return self._check(self._lib.msckf_commit_inject(self._h))
+
     @property
     def n_clones(self) -> int:
         return self._N

@@ -71,40 +71,41 @@ struct AugmentArgs {
     double J[90];         // 6x15: the non-zero columns of J (MSCKF.py:258-261)
 };
 
-// out = sym(M P M^T), M = [I; J]  (MSCKF.py:262-265).  One thread per output element.
-__global__ __launch_bounds__(256) void k_augment(AugmentArgs p) {
-    const int d = p.d, n = d + 6;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n * n) return;
-    const int i = idx / n, j = idx - i * n;
-    double v;
-    if (i < d && j < d) {
-        v = 0.5 * (p.P[(size_t)i * d + j] + p.P[(size_t)j * d + i]);
-    } else if (i >= d && j >= d) {
+// Entry (i, j) of sym(M P M^T), M = [I; J]  (MSCKF.py:262-265); J = the 6x15 non-zero part.
+__device__ __forceinline__ double augment_entry(const double* P, int d, const double* J, int i, int j) {
+    if (i < d && j < d) return 0.5 * (P[(size_t)i * d + j] + P[(size_t)j * d + i]);
+    if (i >= d && j >= d) {
         // S[d+a][d+b] = sum_k (J P)[a][k] J[b][k]; both orders for the symmetrisation
         const int a = i - d, b = j - d;
         double sab = 0.0, sba = 0.0;
         for (int k = 0; k < 15; ++k) {
             double ja = 0.0, jb = 0.0;
             for (int l = 0; l < 15; ++l) {
-                ja = fma(p.J[a * 15 + l], p.P[(size_t)l * d + k], ja);
-                jb = fma(p.J[b * 15 + l], p.P[(size_t)l * d + k], jb);
+                ja = fma(J[a * 15 + l], P[(size_t)l * d + k], ja);
+                jb = fma(J[b * 15 + l], P[(size_t)l * d + k], jb);
             }
-            sab = fma(ja, p.J[b * 15 + k], sab);
-            sba = fma(jb, p.J[a * 15 + k], sba);
+            sab = fma(ja, J[b * 15 + k], sab);
+            sba = fma(jb, J[a * 15 + k], sba);
         }
-        v = 0.5 * (sab + sba);
-    } else {
-        const int a = (i >= d) ? i - d : j - d;       // new clone row
-        const int c = (i >= d) ? j : i;               // old state column
-        double s1 = 0.0, s2 = 0.0;
-        for (int k = 0; k < 15; ++k) {
-            s1 = fma(p.J[a * 15 + k], p.P[(size_t)k * d + c], s1);      // (J P)[a][c]
-            s2 = fma(p.P[(size_t)c * d + k], p.J[a * 15 + k], s2);      // (P J^T)[c][a]
-        }
-        v = 0.5 * (s1 + s2);
+        return 0.5 * (sab + sba);
     }
-    p.out[(size_t)i * n + j] = v;
+    const int a = (i >= d) ? i - d : j - d;       // new clone row
+    const int c = (i >= d) ? j : i;               // old state column
+    double s1 = 0.0, s2 = 0.0;
+    for (int k = 0; k < 15; ++k) {
+        s1 = fma(J[a * 15 + k], P[(size_t)k * d + c], s1);      // (J P)[a][c]
+        s2 = fma(P[(size_t)c * d + k], J[a * 15 + k], s2);      // (P J^T)[c][a]
+    }
+    return 0.5 * (s1 + s2);
+}
+
+// out = sym(M P M^T).  One thread per output element.
+__global__ __launch_bounds__(256) void k_augment(AugmentArgs p) {
+    const int d = p.d, n = d + 6;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n * n) return;
+    const int i = idx / n, j = idx - i * n;
+    p.out[(size_t)i * n + j] = augment_entry(p.P, d, p.J, i, j);
 }
 
 // out[i][j] = P[keep[i]][keep[j]]: rows and columns of removed clones dropped (MSCKF.py:754-757).

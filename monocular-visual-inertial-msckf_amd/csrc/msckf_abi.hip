@@ -33,6 +33,7 @@
 #include "k_lsweep.h"
 #include "k_gather.h"
 #include "k_state.h"
+#include "k_nominal.h"
 #include "k_assoc.h"
 
 using namespace msckf;
@@ -341,6 +342,10 @@ struct msckf_ctx {
     bool have_tracks = false, use_select = false;
     msckf_select_params sel_params{};     // of the last msckf_run_select
     std::vector<double> h_cam[4];         // host mirror of cam_R / cam_t / cam_R0 / cam_t0 (clone bookkeeping, f2)
+    // the nominal state (k_nominal.h): once msckf_set_nominal was called the device arrays lead and the mirror above is only
+    // as fresh as the last msckf_get_nominal / msckf_set_poses
+    bool have_nominal = false;
+    Buf dNom;                             // the record (NOM_RECORD doubles, padded to 200) | Phi_tot of the last batch (225)
     // arenas: what travels together lives together, so each direction is ONE copy through pinned memory
     // (a pageable hipMemcpyAsync costs ~9 us apiece; the 15 + 6 of them were 270 us of the host-inclusive call)
     Buf dPoseArena, dFeatArena, dRawArena, dResArena, dGateArena;     // dRawArena: the tracks in the caller's order (k_gather.h)
@@ -2263,7 +2268,7 @@ void msckf_destroy(msckf_ctx* c) {
                   &c->dLineBase, &c->dLineDir, &c->dLineConf, &c->dLostFor, &c->dTrackedFor, &c->dSelFlags, &c->dWorld,
                   &c->dFlush, &c->dFlushOff, &c->dFeatInfo, &c->dCommBuf, &c->dAssocUV, &c->dAssocRes,
                   &c->dGsEx, &c->dGsFlag, &c->dGsProg, &c->dMProg, &c->dMFlush, &c->dRootFlush, &c->dXRootFlush,
-                  &c->dSplit, &c->dRem};
+                  &c->dSplit, &c->dRem, &c->dNom};
     for (Buf* b : all) if (b->p && !b->view) (void)hipFree(b->p);
     for (Buf* b : {&c->dPoseArena, &c->dFeatArena, &c->dRawArena, &c->dResArena, &c->dGateArena, &c->dPlanArena}) if (b->p) (void)hipFree(b->p);
     for (void* h : {c->hPose, c->hFeat, c->hRes, c->hGate, c->hP}) if (h) (void)hipHostFree(h);
@@ -3244,7 +3249,14 @@ int msckf_augment(msckf_ctx* c, const double* J15, const double* R, const double
     c->h_cam[2].insert(c->h_cam[2].end(), R, R + 9); c->h_cam[3].insert(c->h_cam[3].end(), t, t + 3);
     c->N += 1; c->d = 15 + 6 * c->N; c->dc = 6 * c->N;
     seat_result_views(c);
-    if (int rc = upload_poses(c)) return rc;
+    if (c->have_nominal) {                // the mirror is stale: only the new clone's pose travels
+        ClonePoseArgs q{};
+        std::memcpy(q.R, R, sizeof(q.R)); std::memcpy(q.t, t, sizeof(q.t));
+        q.camR = ptr<double>(c->dCamR); q.camT = ptr<double>(c->dCamT); q.camR0 = ptr<double>(c->dCamR0); q.camT0 = ptr<double>(c->dCamT0);
+        q.slot = c->N - 1;
+        hipLaunchKernelGGL(k_set_clone_pose, dim3(1), dim3(64), 0, c->stream, q);
+        HIPCHK(c, hipGetLastError());
+    } else if (int rc = upload_poses(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     invalidate_batch(c);
     return MSCKF_OK;
@@ -3280,7 +3292,13 @@ int msckf_remove_clones(msckf_ctx* c, int32_t n, const int32_t* slots) {
     for (int q = 0; q < 4; ++q) c->h_cam[q].swap(nc[q]);
     c->N -= n; c->d = 15 + 6 * c->N; c->dc = 6 * c->N;
     seat_result_views(c);
-    if (int rc = upload_poses(c)) return rc;
+    if (c->have_nominal) {                // the device arrays lead (an injection moved them): compact them where they are
+        if (c->N > 0) {
+            hipLaunchKernelGGL(k_compact_poses, dim3(1), dim3(256), (size_t)c->N * 24 * 8, c->stream, ptr<double>(c->dCamR), ptr<double>(c->dCamT),
+                               ptr<double>(c->dCamR0), ptr<double>(c->dCamT0), ptr<int>(c->dKeep), c->N);
+            HIPCHK(c, hipGetLastError());
+        }
+    } else if (int rc = upload_poses(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     invalidate_batch(c);
     return MSCKF_OK;
@@ -3308,6 +3326,103 @@ int msckf_get_covariance(msckf_ctx* c, double* P, int32_t* N) {
         HIPCHK(c, hipMemcpyAsync(P, c->dP.p, (size_t)c->d * c->d * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return MSCKF_OK;
+}
+
+// ---- the nominal state beside the covariance (k_nominal.h) -------------------------------------------------------
+static_assert(sizeof(msckf_nominal) == (size_t)NOM_DOUBLES * 8, "msckf_nominal and the record's layout (k_nominal.h) differ");
+static_assert(MSCKF_IMU_BATCH_MAX == IMU_BATCH_MAX && sizeof(ImuBatchArgs) <= 4096, "the samples travel in the kernel arguments");
+
+int msckf_set_nominal(msckf_ctx* c, const msckf_nominal* s) {
+    if (!c || !s) return MSCKF_ERR_ARG;
+    if (!c->have_state) return MSCKF_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure(c, c->dNom, (size_t)(200 + 225) * 8, true)) return rc;
+    double rec[200] = {0};
+    std::memcpy(rec, s, sizeof(*s));
+    HIPCHK(c, hipMemcpyAsync(c->dNom.p, rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->have_nominal = true;
+    return MSCKF_OK;
+}
+
+int msckf_get_nominal(msckf_ctx* c, msckf_nominal* s, double* cam_R, double* cam_t) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->have_nominal) return MSCKF_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = c->N, mN = c->maxN;
+    if (c->pose_busy) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream_up)); c->pose_busy = false; }
+    double rec[NOM_DOUBLES];
+    HIPCHK(c, hipMemcpyAsync(rec, c->dNom.p, sizeof(rec), hipMemcpyDeviceToHost, c->stream));
+    if (N > 0) HIPCHK(c, hipMemcpyAsync(c->hPose, c->dPoseArena.p, 24 * mN * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (s) std::memcpy(s, rec, sizeof(*s));
+    if (N > 0) {                          // the mirror is fresh again
+        const double* h = static_cast<const double*>(c->hPose);
+        c->h_cam[0].assign(h, h + N * 9); c->h_cam[1].assign(h + 9 * mN, h + 9 * mN + N * 3);
+        c->h_cam[2].assign(h + 12 * mN, h + 12 * mN + N * 9); c->h_cam[3].assign(h + 21 * mN, h + 21 * mN + N * 3);
+        if (cam_R) std::memcpy(cam_R, h, N * 72);
+        if (cam_t) std::memcpy(cam_t, h + 9 * mN, N * 24);
+    }
+    return MSCKF_OK;
+}
+
+int msckf_propagate_imu(msckf_ctx* c, int32_t n, const double* gyro, const double* acc, const double* dt) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->have_nominal) return MSCKF_ERR_STATE;
+    if (n < 1 || n > MSCKF_IMU_BATCH_MAX || !gyro || !acc || !dt) return MSCKF_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    ImuBatchArgs a;
+    a.P = ptr<double>(c->dP); a.d = c->d; a.n = n;
+    a.nom = ptr<double>(c->dNom); a.phi_tot = a.nom + 200;
+    for (int k = 0; k < n; ++k) {
+        std::memcpy(a.s + 7 * k, gyro + 3 * k, 24);
+        std::memcpy(a.s + 7 * k + 3, acc + 3 * k, 24);
+        a.s[7 * k + 6] = dt[k];
+    }
+    hipLaunchKernelGGL(k_propagate_imu, dim3(1), dim3(256), 0, c->stream, a);
+    if (c->d > 15) {
+        const int nb = (c->d - 15 + 15) / 16;
+        hipLaunchKernelGGL(k_propagate_strip, dim3(nb, 1 + nb), dim3(256), 0, c->stream, ptr<double>(c->dP), c->d, (const double*)a.phi_tot);
+    }
+    HIPCHK(c, hipGetLastError());
+    c->main_busy = true;
+    c->ran = false;                       // results of a previous update refer to the old prior
+    return MSCKF_OK;
+}
+
+int msckf_augment_imu(msckf_ctx* c) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->have_nominal) return MSCKF_ERR_STATE;
+    if (c->N + 1 > c->maxN) return MSCKF_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    AugmentImuArgs a{};
+    a.P = ptr<double>(c->dP); a.out = ptr<double>(c->dB2); a.d = c->d; a.nom = ptr<double>(c->dNom);
+    a.camR = ptr<double>(c->dCamR); a.camT = ptr<double>(c->dCamT); a.camR0 = ptr<double>(c->dCamR0); a.camT0 = ptr<double>(c->dCamT0);
+    a.slot = c->N;
+    const int n = c->d + 6;
+    hipLaunchKernelGGL(k_augment_imu, dim3((n * n + 255) / 256), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    std::swap(c->dP, c->dB2);             // as msckf_augment
+    for (int q = 0; q < 4; ++q) c->h_cam[q].insert(c->h_cam[q].end(), (q & 1) ? 3 : 9, 0.0);   // (a place in the mirror; msckf_get_nominal fills it)
+    c->N += 1; c->d = 15 + 6 * c->N; c->dc = 6 * c->N;
+    seat_result_views(c);
+    invalidate_batch(c);
+    c->main_busy = true;
+    return MSCKF_OK;
+}
+
+int msckf_commit_inject(msckf_ctx* c) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->have_nominal) return MSCKF_ERR_STATE;
+    const int rc = msckf_commit_covariance(c);
+    if (rc != MSCKF_OK) return rc;        // no-op or failed update: P and the record stay as they are
+    InjectArgs a{};
+    a.dx = ptr<double>(c->dDx); a.nom = ptr<double>(c->dNom); a.N = c->N;
+    a.camR = ptr<double>(c->dCamR); a.camT = ptr<double>(c->dCamT); a.camR0 = ptr<double>(c->dCamR0); a.camT0 = ptr<double>(c->dCamT0);
+    hipLaunchKernelGGL(k_inject, dim3((c->N + 1 + 63) / 64), dim3(64), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    c->main_busy = true;
     return MSCKF_OK;
 }
 

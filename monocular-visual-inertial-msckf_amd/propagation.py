@@ -56,17 +56,29 @@ def imu_transition(R, t, v, R0, t0, v0, gyro, acc, dt, gravity, noise, planet_ra
     return Phi, Q
 
 
+def _hom(R, t):
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = np.asarray(t, dtype=np.float64).reshape(3)
+    return T
+
+
+def _extrinsics_hom(T_W_I, T_W_C):
+    return np.linalg.inv(_hom(*T_W_I)) @ _hom(*T_W_C)                 # :252 (Isometry3D.inv / __mul__)
+
+
+def extrinsics(T_W_I, T_W_C):
+    """(R, t) of the static camera frame in the IMU frame, `T_W_I.inv() * T_W_C` (reference `MSCKF.py:252`)."""
+    T_I_C = _extrinsics_hom(T_W_I, T_W_C)
+    return T_I_C[:3, :3].copy(), T_I_C[:3, 3].copy()
+
+
 def augmentation(imu_R, imu_t, T_W_I, T_W_C):
     """Pose of the new clone and the non-zero 6x15 block of the augmentation Jacobian
     (reference `MSCKF.py:252-261`).  `T_W_I`, `T_W_C`: (R, t) of the static IMU and camera
     frames (`IMU.py:26`, `MSCKF.py:89`)."""
-    def hom(R, t):
-        T = np.eye(4)
-        T[:3, :3] = R
-        T[:3, 3] = np.asarray(t, dtype=np.float64).reshape(3)
-        return T
-    T_I_C = np.linalg.inv(hom(*T_W_I)) @ hom(*T_W_C)                  # :252 (Isometry3D.inv / __mul__)
-    T_W_Ci = hom(imu_R, imu_t) @ T_I_C                                # :253
+    T_I_C = _extrinsics_hom(T_W_I, T_W_C)
+    T_W_Ci = _hom(imu_R, imu_t) @ T_I_C                               # :253
     J = np.zeros((6, 15))
     J[0:3, 0:3] = T_I_C[:3, :3].T                                     # :259
     J[3:6, 0:3] = _hat(np.asarray(imu_R, dtype=np.float64) @ T_I_C[:3, 3])   # :260

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Host time per frame of the resident filter loop AROUND the update, before and after the resident nominal state.
+
+The 30-clone reference run (`tests/golden/window30/seq_window30.npz`) is driven frame by frame through
+  (a) the loop of `tests/test_gpu_window30.py::test_resident_window30_run_tracks_the_reference`: per IMU sample
+      `propagation.imu_transition` + `propagate`, `propagation.augmentation` + `augment`, after the update
+      `commit_covariance` + `set_poses`, `remove_clones` (IMU states and corrected poses come from the fixture: the host
+      integration and injection a real caller also pays are NOT charged to it);
+  (b) `propagate_imu` (one call per frame), `augment_imu`, `commit_inject`, `remove_clones`.
+Timed: everything of a frame except `set_features ... result` (the update is the same in both), up to a stream sync at
+the end of each timed stretch.  Both loops run in one process on engines of one size, interleaved run by run after one
+untimed run each.  `--samples 20` splits every sample's dt in five (4 -> 20 samples per frame).
+
+    python tools/frame_loop.py [--samples 4|20] [--runs 7] [--loop a|b|both] [--out FILE]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import nominal_ref                                   # noqa: E402
+import window30                                      # noqa: E402
+from window30 import AUGMENT, PROCESS, PRUNE, REMOVE  # noqa: E402
+
+
+def frames_of(run, sub):
+    """Per frame: the IMU samples (each split in `sub`) with the states loop (a) needs, and the ops that follow."""
+    z = run.z
+    gyro_raw, acc_raw = nominal_ref.raw_samples(run)
+    frames = []
+    for kind, idx, o in nominal_ref.imu_groups(run):
+        if kind == "imu":
+            samples = []
+            for i in idx:
+                R, t, v = z["imu_R0"][i], z["imu_t0"][i], z["imu_v0"][i]
+                dt = float(z["imu_dt"][i]) / sub
+                for _ in range(sub):
+                    R1, t1, v1, _ = nominal_ref.integrate(R, t, v, z["imu_acc"][i], z["imu_gyro"][i], dt, z["gravity"], z["imu_w_planet"][i])
+                    samples.append(dict(R=R1, t=t1, v=v1, R0=R, t0=t, v0=v, gyro=z["imu_gyro"][i], acc=z["imu_acc"][i], dt=dt,
+                                        w_planet=z["imu_w_planet"][i], gyro_raw=gyro_raw[i], acc_raw=acc_raw[i]))
+                    R, t, v = R1, t1, v1
+            frames.append(dict(samples=samples, ops=[]))
+        else:
+            frames[-1]["ops"].append((kind, idx))
+    return frames
+
+
+def drive(run, eng, frames, loop):
+    """One pass over the run; returns the timed seconds of every frame."""
+    from msckf_amd import propagation
+    z = run.z
+    params = run.select_params()
+    eng.set_prior(z["P0"], z["gravity"], z["K"], run.sigma)
+    if loop == "b":
+        eng.set_nominal(z["imu_R0"][0], z["imu_t0"][0], z["imu_v0"][0], z["gravity"], z["Qc"],
+                        T_W_I=(z["T_W_I_R"], z["T_W_I_t"]), T_W_C=(z["T_W_C_R"], z["T_W_C_t"]))
+    ext = ((z["T_W_I_R"], z["T_W_I_t"]), (z["T_W_C_R"], z["T_W_C_t"]))
+    out = []
+    clock = time.perf_counter
+    for fr in frames:
+        t0 = clock()
+        sm = fr["samples"]
+        if loop == "a":
+            for s in sm:
+                Phi, Q = propagation.imu_transition(s["R"], s["t"], s["v"], s["R0"], s["t0"], s["v0"], s["gyro"], s["acc"], s["dt"],
+                                                    z["gravity"], z["Qc"], s["w_planet"])
+                eng.propagate(Phi, Q)
+        else:
+            eng.propagate_imu(np.array([s["gyro_raw"] for s in sm]), np.array([s["acc_raw"] for s in sm]), np.array([s["dt"] for s in sm]))
+        spent = 0.0
+        for kind, idx in fr["ops"]:
+            if kind == AUGMENT:
+                if loop == "a":
+                    a = run.aug(idx)
+                    J, cR, ct = propagation.augmentation(a["imu_R"], a["imu_t"], *ext)
+                    eng.augment(J, cR, ct)
+                else:
+                    eng.augment_imu()
+            elif kind in (PROCESS, PRUNE):
+                c = run.call(idx)
+                N = eng.n_clones
+                eng.sync()
+                spent += clock() - t0
+                # ---- the update: not timed --------------------------------------------------------------------------
+                prob = run.problem(c, np.zeros((15 + 6 * N,) * 2), np.zeros((N, 3, 3)), np.zeros((N, 3)))
+                eng.set_features(prob)
+                eng.set_tracks(run.tracks(c))
+                eng.run_select(params, prob.K)
+                n_valid = int(eng.selection().valid.sum())
+                status = 1
+                if n_valid:
+                    eng.run()
+                    status = eng.result().status
+                # -----------------------------------------------------------------------------------------------------
+                t0 = clock()
+                if n_valid:
+                    if loop == "a":
+                        eng.commit_covariance()
+                    else:
+                        eng.commit_inject()
+                if kind == PRUNE:
+                    eng.remove_clones(c["rm"])
+                if loop == "a" and status == 0:
+                    eng.set_poses(c["post_R"], c["post_t"])
+            elif kind == REMOVE:
+                eng.remove_clones(run.call(idx)["rm"])
+        eng.sync()
+        out.append(spent + clock() - t0)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--samples", type=int, default=4, choices=(4, 20))
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--loop", default="both", choices=("a", "b", "both"))
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    from msckf_amd.api import UpdateEngine
+    run = window30.Run()
+    frames = frames_of(run, args.samples // 4)
+    loops = ["a", "b"] if args.loop == "both" else [args.loop]
+    engines = {lp: UpdateEngine(max_clones=31, max_features=4096, max_track=31) for lp in loops}
+    per_run = {lp: [] for lp in loops}
+    for lp in loops:
+        drive(run, engines[lp], frames, lp)                      # warm-up: first launches, plan cache, worker threads
+    for _ in range(args.runs):
+        for lp in loops:
+            per_run[lp].append(drive(run, engines[lp], frames, lp))
+    lines = [f"frame loop around the update, {len(frames)} frames, {args.samples} IMU samples per frame, {args.runs} runs; us per frame"]
+    for lp in loops:
+        t = np.array(per_run[lp]) * 1e6
+        meds = np.median(t, axis=1)
+        lines.append(f"  ({lp}) median {np.median(t):8.1f}   p10 {np.percentile(t, 10):8.1f}   p90 {np.percentile(t, 90):8.1f}   "
+                     f"medians of the runs: min {meds.min():8.1f}  max {meds.max():8.1f}")
+    if len(loops) == 2:
+        ma, mb = (np.median(np.array(per_run[lp]) * 1e6, axis=1) for lp in loops)
+        lines.append(f"  (a) / (b) of the runs' medians: {np.median(ma) / np.median(mb):.2f}x   "
+                     f"spread of a run's median: (a) {100 * (ma.max() - ma.min()) / np.median(ma):.1f} %, (b) {100 * (mb.max() - mb.min()) / np.median(mb):.1f} %")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+    for e in engines.values():
+        e.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -295,6 +295,46 @@ int msckf_augment_imu(msckf_ctx* ctx);
  * and the record untouched.  Asynchronous wherever msckf_commit_covariance is. */
 int msckf_commit_inject(msckf_ctx* ctx);
 
+/* ---- the track store: views and bases resident, batches by track id -------- *
+ * The feature batch is the last input of the resident loop that depends on the clone poses: every Line.base is the
+ * clone's own position array (MSCKF.py:410, :430-431) and every InverseDepthPoint.base that of the clone the track was
+ * created in (geometry.py:55), so both move with each injection.  The store keeps every floating-point field of the
+ * tracks in HBM (fp64 in both dtypes; capacity max_features tracks x max_track views, allocated on first use) and which
+ * track has views in which clone slots on the host, inside the context.  A frame sends its new keypoints
+ * (msckf_tracks_observe) and asks for a batch by track id (msckf_tracks_load); the bases are resolved on the device from
+ * the resident clone positions.  Works on any context with a state; the "newest clone" is slot N - 1.
+ *   MSCKF.add_camera_measurements :403-411, :420-434  -> msckf_tracks_observe
+ *   MSCKF.get_valid_features / update candidates      -> msckf_tracks_load      (= msckf_set_features + msckf_set_tracks)
+ *   MSCKF.remove_features :739-741                    -> msckf_tracks_remove
+ *   MSCKF.remove_cameras :760-779                     -> msckf_remove_clones    (views dropped, slots renumbered, anchors frozen)
+ * msckf_run_select on a batch that came from the store writes the refreshed m / rho of the MSCKF_SEL_REFRESHED tracks back
+ * to their rows (the reference's refresh persists, :488), in the stream behind the selection kernel; deleting tracks
+ * (msckf_tracks_remove, msckf_remove_clones) ends that for the loaded batch, so select first, as the reference does.
+ * msckf_set_state empties the store (slots lose their meaning); msckf_set_poses, msckf_augment and msckf_augment_imu leave
+ * it alone.  An erroring call leaves the store exactly as it was.  A caller who never uses these calls sees no change. */
+int msckf_tracks_reset(msckf_ctx* ctx);
+/* One view of the newest clone for each listed track: dir = R_new (K^-1 [u, v, 1]) with the resident rotation and the K^-1
+ * of msckf_set_state, conf = score.  An unknown id creates a track: anchor = the newest clone, m = dir / |dir|
+ * (geometry.py:56-58), rho = 0.1 (:59).  Asynchronous.  MSCKF_ERR_STATE when N = 0; MSCKF_ERR_DUP_SLOT when a track already
+ * has a view of the newest clone or an id appears twice; MSCKF_ERR_ARG past either capacity (or a negative id). */
+int msckf_tracks_observe(msckf_ctx* ctx, int32_t n, const int32_t* ids, const double* uv /*2n*/, const double* score /*n*/);
+/* Delete tracks.  An unknown (or repeated) id: MSCKF_ERR_ARG, nothing deleted. */
+int msckf_tracks_remove(msckf_ctx* ctx, int32_t n, const int32_t* ids);
+/* The effect of msckf_set_features + msckf_set_tracks for the listed tracks in the listed order (the input order of
+ * accepted[], flags[] and msckf_get_selection), with the same plan: line_base = the resident position of each view's clone,
+ * idp_base = that of the anchor clone or the frozen base; lost_for / tracked_for are the front end's counters.  Asynchronous
+ * wherever msckf_set_features is.  MSCKF_ERR_ARG for an unknown or repeated id. */
+int msckf_tracks_load(msckf_ctx* ctx, int32_t F, const int32_t* ids, const int32_t* lost_for, const int32_t* tracked_for);
+/* One track as it stands on the device (tests, logging; blocking; any output may be NULL): M views, slots[M], uv[2M],
+ * dir[3M], conf[M], line_base[3M] and idp_base[3] resolved as msckf_tracks_load would, idp_m[3], idp_rho, anchor_slot
+ * (-1 once the anchor is frozen). */
+int msckf_tracks_get(msckf_ctx* ctx, int32_t id, int32_t* M, int32_t* slots, double* uv, double* dir, double* conf,
+                     double* line_base, double* idp_base, double* idp_m, double* idp_rho, int32_t* anchor_slot);
+int msckf_tracks_count(msckf_ctx* ctx, int32_t* n_tracks, int32_t* n_views);
+/* The ids of the tracks the last msckf_remove_clones deleted (left without a view): up to `cap` of them into ids;
+ * returns how many there were (>= 0). */
+int msckf_tracks_dropped(msckf_ctx* ctx, int32_t* ids, int32_t cap);
+
 /* ---- feature-sharded path (one context per GPU / rank) ------------------ *
  * Each rank holds a shard of the features and the full state.  It runs K1-K5
  * locally and exports its compressed block [R | Q^T r]: (6N) x (6N+1) doubles,

@@ -35,6 +35,8 @@ SYMBOLS = [
     "msckf_set_exchange_mask", "msckf_result_range_doubles", "msckf_get_shared_result", "msckf_set_exchange_span",
     "msckf_debug_split", "msckf_debug_set_rem_direct_rows", "msckf_exchange_split_rule", "msckf_set_exchange_split",
     "msckf_set_nominal", "msckf_get_nominal", "msckf_propagate_imu", "msckf_augment_imu", "msckf_commit_inject",
+    "msckf_tracks_reset", "msckf_tracks_observe", "msckf_tracks_remove", "msckf_tracks_load", "msckf_tracks_get",
+    "msckf_tracks_count", "msckf_tracks_dropped",
 ]
 
 
@@ -212,6 +214,15 @@ def load():
     for name in ("msckf_augment_imu", "msckf_commit_inject"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = C.c_int
+    lib.msckf_tracks_reset.argtypes = [vp]
+    lib.msckf_tracks_observe.argtypes = [vp, C.c_int32, _ip, _dp, _dp]
+    lib.msckf_tracks_remove.argtypes = [vp, C.c_int32, _ip]
+    lib.msckf_tracks_load.argtypes = [vp, C.c_int32, _ip, _ip, _ip]
+    lib.msckf_tracks_get.argtypes = [vp, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]
+    lib.msckf_tracks_count.argtypes = [vp, _ip, _ip]
+    lib.msckf_tracks_dropped.argtypes = [vp, _ip, C.c_int32]
+    for name in ("reset", "observe", "remove", "load", "get", "count", "dropped"):
+        getattr(lib, "msckf_tracks_" + name).restype = C.c_int
     lib.msckf_debug_split.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.msckf_debug_split.restype = C.c_int
     lib.msckf_debug_set_rem_direct_rows.argtypes = [vp, C.c_int32]

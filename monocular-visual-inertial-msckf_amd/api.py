@@ -415,6 +415,68 @@ class UpdateEngine:
         """`commit_covariance` + the state injection of `MSCKF.correct` (reference `MSCKF.py:616-661`) on the device."""
         return self._check(self._lib.msckf_commit_inject(self._h))
 
+    # -- the track store: views and bases resident, batches by track id --------
+    def tracks_reset(self):
+        """Empty the track store."""
+        self._check(self._lib.msckf_tracks_reset(self._h), allow_noop=False)
+
+    def tracks_observe(self, ids, uv, score):
+        """One view of the newest clone for each listed track (reference `MSCKF.py:403-411`, `:420-434`): `uv` (n, 2)
+        pixels, `score` (n,).  Unknown ids create tracks.  Direction, line and inverse-depth point are formed on the
+        device from the resident pose; async."""
+        i, u, s = _ffi.i32(np.asarray(ids).reshape(-1)), _ffi.f64(uv).reshape(-1), _ffi.f64(score).reshape(-1)
+        if u.size != 2 * i.size or s.size != i.size:
+            raise ValueError("uv is (n, 2), score (n,)")
+        self._check(self._lib.msckf_tracks_observe(self._h, int(i.size), _ffi.iptr(i), _ffi.dptr(u), _ffi.dptr(s)),
+                    allow_noop=False)
+
+    def tracks_remove(self, ids):
+        """Delete tracks (reference `MSCKF.py:739-741`)."""
+        i = _ffi.i32(np.asarray(ids).reshape(-1))
+        self._check(self._lib.msckf_tracks_remove(self._h, int(i.size), _ffi.iptr(i)), allow_noop=False)
+
+    def load_tracks(self, ids, lost_for, tracked_for):
+        """`set_features` + `set_tracks` for the listed tracks of the store, in the listed order; their bases are the
+        resident clone positions.  `lost_for`, `tracked_for`: the front end's counters."""
+        i = _ffi.i32(np.asarray(ids).reshape(-1))
+        lo, tr = _ffi.i32(np.asarray(lost_for).reshape(-1)), _ffi.i32(np.asarray(tracked_for).reshape(-1))
+        if lo.size != i.size or tr.size != i.size:
+            raise ValueError("lost_for and tracked_for are (F,)")
+        self._check(self._lib.msckf_tracks_load(self._h, int(i.size), _ffi.iptr(i), _ffi.iptr(lo), _ffi.iptr(tr)),
+                    allow_noop=False)
+        self._F = int(i.size)
+
+    def track(self, track_id: int) -> dict:
+        """One track as it stands on the device (waits for the stream): `slots, uv, dir, conf, line_base, idp_base,
+        idp_m, idp_rho, anchor_slot` (-1 once the anchor clone was removed: the base is frozen)."""
+        V = _ffi.MAX_TRACK
+        M, anchor = C.c_int32(0), C.c_int32(0)
+        rho = C.c_double(0)
+        slots = np.zeros(V, dtype=np.int32)
+        uv, d, conf, lb = np.zeros((V, 2)), np.zeros((V, 3)), np.zeros(V), np.zeros((V, 3))
+        ib, m = np.zeros(3), np.zeros(3)
+        self._check(self._lib.msckf_tracks_get(
+            self._h, int(track_id), C.addressof(M), _ffi.iptr(slots), _ffi.dptr(uv), _ffi.dptr(d), _ffi.dptr(conf),
+            _ffi.dptr(lb), _ffi.dptr(ib), _ffi.dptr(m), C.addressof(rho), C.addressof(anchor)), allow_noop=False)
+        n = int(M.value)
+        return dict(slots=slots[:n].copy(), uv=uv[:n].copy(), dir=d[:n].copy(), conf=conf[:n].copy(),
+                    line_base=lb[:n].copy(), idp_base=ib, idp_m=m, idp_rho=float(rho.value), anchor_slot=int(anchor.value))
+
+    def tracks_count(self):
+        """(tracks, views) the store holds."""
+        nt, nv = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.msckf_tracks_count(self._h, C.addressof(nt), C.addressof(nv)), allow_noop=False)
+        return int(nt.value), int(nv.value)
+
+    def tracks_dropped(self) -> np.ndarray:
+        """Ids of the tracks the last `remove_clones` deleted (left without a view)."""
+        n = self._lib.msckf_tracks_dropped(self._h, None, 0)
+        if n < 0:
+            self._check(n, allow_noop=False)
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        self._lib.msckf_tracks_dropped(self._h, _ffi.iptr(out), int(n))
+        return out[:n].copy()
+
     @property
     def n_clones(self) -> int:
         return self._N

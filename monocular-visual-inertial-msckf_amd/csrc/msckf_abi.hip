@@ -12,6 +12,8 @@
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <unordered_map>
+#include <unordered_set>
 #include <pthread.h>
 #include <sched.h>
 #include <cmath>
@@ -35,6 +37,7 @@
 #include "k_state.h"
 #include "k_nominal.h"
 #include "k_assoc.h"
+#include "k_tracks.h"
 
 using namespace msckf;
 
@@ -110,6 +113,14 @@ struct Buf {
 inline void set_view(Buf& b, void* base, size_t off, size_t bytes) {
     b.p = static_cast<char*>(base) + off; b.bytes = bytes; b.view = true;
 }
+
+// a pinned host image that kernels read where it lies: the event says when the last reader is through
+struct PinStage {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+};
 
 double now_us() {
     using namespace std::chrono;
@@ -466,6 +477,18 @@ struct msckf_ctx {
     bool main_busy = false;                      // the main stream holds work nobody has waited for
     bool run_pending = false;                    // ... a pipeline / merge among it (kernels that read the K5 plan and the workspace)
     bool wide_concurrent = true;          // MSCKF_WIDE_STREAM=0: everything on one stream
+    // The track store (k_tracks.h): the floating-point fields of the tracks in HBM, which track has views in which clone slots
+    // here.  Rows are handed out by this mirror; a row's views are in ascending slot order (they are appended for the newest
+    // clone and the renumbering of msckf_remove_clones is monotone).
+    Buf dTrk, dTrkRows, dTrkRowSorted;
+    TrackStore trk{};
+    bool trk_ready = false;
+    std::vector<int> trk_id, trk_M, trk_anchor, trk_slots;   // per row: id (-1: free), views, anchor slot (-1: frozen), [row][V] slots
+    std::vector<int> trk_free, trk_dropped;                  // free rows (a stack); ids the last msckf_remove_clones deleted
+    std::unordered_map<int, int> trk_row_of;                 // id -> row
+    long long trk_views = 0;
+    bool batch_from_store = false;        // the current batch came through msckf_tracks_load: msckf_run_select writes refreshed points back
+    PinStage trk_obs_stage, trk_load_stage;
     long run_serial = 0;                  // bumped by every pipeline / merge launch
     long fetched_serial = -1;             // the run whose return code msckf_get_result derived last ...
     int fetched_rc = 0;                   // ... and that code: msckf_commit_covariance need not read the gate results again
@@ -587,6 +610,7 @@ void invalidate_batch(msckf_ctx* c) {
     c->use_select = false;
     c->ran = false;
     c->F = 0;
+    c->batch_from_store = false;
 }
 
 // Tracks that span more than WIDE_SPAN clone slots are SPLIT (k_feature.h: two-level nullspace basis) wherever a batch is
@@ -2045,6 +2069,129 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
 
 }  // namespace
 
+// ---- the track store (k_tracks.h): host mirror and launches ------------------------------------------------------
+namespace {
+
+// What msckf_tracks_load hands to the batch upload in place of the caller's floats: the rows of the candidates (input order) and
+// the front end's counters.  The integers (view_ptr, obs_slot) come from the store's mirror; k_track_emit writes the floats.
+struct TrackEmitSrc { const int* rows; const int32_t* lost; const int32_t* tracked; };
+
+// the image is free to be rewritten (its last reader is through) and holds `bytes`
+int stage_acquire(msckf_ctx* c, PinStage& s, size_t bytes) {
+    if (s.pending) { HIPCHK(c, hipEventSynchronize(s.ev)); s.pending = false; }
+    if (!s.ev) HIPCHK(c, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    if (s.cap < bytes) {
+        if (s.p) HIPCHK(c, hipHostFree(s.p));
+        s.p = nullptr; s.cap = 0;
+        const size_t want = std::max<size_t>(2 * bytes, 4096);
+        HIPCHK(c, hipHostMalloc(&s.p, want));
+        s.cap = want;
+    }
+    return MSCKF_OK;
+}
+int stage_release(msckf_ctx* c, PinStage& s) {
+    HIPCHK(c, hipEventRecord(s.ev, c->stream));
+    s.pending = true;
+    return MSCKF_OK;
+}
+
+void tracks_clear(msckf_ctx* c) {
+    c->trk_row_of.clear();
+    c->trk_dropped.clear();
+    c->trk_views = 0;
+    c->batch_from_store = false;
+    if (!c->trk_ready) return;
+    const int T = c->maxF;
+    std::fill(c->trk_id.begin(), c->trk_id.end(), -1);
+    std::fill(c->trk_M.begin(), c->trk_M.end(), 0);
+    c->trk_free.resize(T);
+    for (int r = 0; r < T; ++r) c->trk_free[r] = T - 1 - r;         // row 0 goes out first
+}
+
+// capacity max_features tracks x max_track views, allocated on first use
+int tracks_ensure(msckf_ctx* c) {
+    if (c->trk_ready) return MSCKF_OK;
+    const size_t T = c->maxF, V = c->maxM, TV = T * V;
+    const size_t o_uv = 0, o_dir = o_uv + TV * 16, o_conf = o_dir + TV * 24, o_m = o_conf + TV * 8, o_rho = o_m + T * 24;
+    const size_t o_frozen = o_rho + T * 8, o_slot = o_frozen + T * 24, o_anchor = o_slot + TV * 4, o_count = o_anchor + T * 4;
+    if (int rc = ensure(c, c->dTrk, o_count + T * 4, true)) return rc;
+    if (int rc = ensure(c, c->dTrkRows, T * 4)) return rc;
+    char* b = static_cast<char*>(c->dTrk.p);
+    TrackStore& s = c->trk;
+    s.uv = reinterpret_cast<double*>(b + o_uv); s.dir = reinterpret_cast<double*>(b + o_dir);
+    s.conf = reinterpret_cast<double*>(b + o_conf); s.m = reinterpret_cast<double*>(b + o_m);
+    s.rho = reinterpret_cast<double*>(b + o_rho); s.frozen = reinterpret_cast<double*>(b + o_frozen);
+    s.slot = reinterpret_cast<int*>(b + o_slot); s.anchor = reinterpret_cast<int*>(b + o_anchor);
+    s.count = reinterpret_cast<int*>(b + o_count); s.V = (int)V;
+    c->trk_id.assign(T, -1); c->trk_M.assign(T, 0); c->trk_anchor.assign(T, -1); c->trk_slots.assign(TV, 0);
+    c->trk_ready = true;
+    tracks_clear(c);
+    return MSCKF_OK;
+}
+
+inline void tracks_free_row(msckf_ctx* c, int row) {
+    c->trk_row_of.erase(c->trk_id[row]);
+    c->trk_views -= c->trk_M[row];
+    c->trk_id[row] = -1; c->trk_M[row] = 0;
+    c->trk_free.push_back(row);
+    c->batch_from_store = false;          // (the row may be handed out again: a loaded batch no longer writes refreshed points back)
+}
+
+int launch_track_emit(msckf_ctx* c, const TrackEmitSrc* src, int F, int sumM, const int32_t* view_ptr,
+                      const std::vector<int>& h_view, char* draw, size_t r_base, size_t r_m, size_t r_rho, size_t r_slot) {
+    int rc = MSCKF_OK;
+    auto E = [&](Buf& b, size_t bytes) { if (rc == MSCKF_OK) rc = ensure(c, b, bytes); };
+    E(c->dLineBase, (size_t)sumM * 24); E(c->dLineDir, (size_t)sumM * 24); E(c->dLineConf, (size_t)sumM * 8);
+    E(c->dLostFor, (size_t)F * 4); E(c->dTrackedFor, (size_t)F * 4); E(c->dSelFlags, (size_t)F); E(c->dWorld, (size_t)F * 24);
+    E(c->dTrkRowSorted, (size_t)F * 4);
+    if (rc != MSCKF_OK) return rc;
+    if (int rcs = stage_acquire(c, c->trk_load_stage, (size_t)F * sizeof(TrackEmitRec))) return rcs;
+    TrackEmitRec* rec = static_cast<TrackEmitRec*>(c->trk_load_stage.p);
+    for (int sidx = 0; sidx < F; ++sidx) {
+        const int f = c->perm[sidx];
+        rec[f] = TrackEmitRec{src->rows[f], view_ptr[f + 1] - view_ptr[f], view_ptr[f], h_view[sidx], sidx, src->lost[f], src->tracked[f], 0};
+    }
+    TrackEmitArgs a{};
+    a.s = c->trk; a.rec = rec; a.F = F; a.cam_t = ptr<double>(c->dCamT);
+    a.uv_raw = reinterpret_cast<double*>(draw); a.slot_raw = reinterpret_cast<int*>(draw + r_slot);
+    a.base_raw = reinterpret_cast<double*>(draw + r_base); a.m_raw = reinterpret_cast<double*>(draw + r_m);
+    a.rho_raw = reinterpret_cast<double*>(draw + r_rho);
+    a.line_base = ptr<double>(c->dLineBase); a.line_dir = ptr<double>(c->dLineDir); a.line_conf = ptr<double>(c->dLineConf);
+    a.lost_for = ptr<int>(c->dLostFor); a.tracked_for = ptr<int>(c->dTrackedFor); a.row_sorted = ptr<int>(c->dTrkRowSorted);
+    hipLaunchKernelGGL(k_track_emit, dim3((F + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return stage_release(c, c->trk_load_stage);
+}
+
+// msckf_remove_clones on a context whose store holds tracks (reference MSCKF.py:760-779): drop[s] != 0 for the clones that go
+int tracks_drop_clones(msckf_ctx* c, const std::vector<char>& drop) {
+    c->trk_dropped.clear();
+    if (!c->trk_ready || c->trk_row_of.empty()) return MSCKF_OK;
+    const int N = c->N, V = c->maxM;
+    TrackDropArgs a{};
+    for (int s = 0, k = 0; s < N; ++s) a.remap[s] = drop[s] ? (short)-1 : (short)k++;
+    std::vector<int> rows;
+    rows.reserve(c->trk_row_of.size());
+    for (int r = 0; r < c->maxF; ++r) if (c->trk_id[r] >= 0) rows.push_back(r);
+    a.s = c->trk; a.rows = ptr<int>(c->dTrkRows); a.n = (int)rows.size(); a.cam_t = ptr<double>(c->dCamT);
+    HIPCHK(c, hipMemcpyAsync(c->dTrkRows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_track_drop, dim3((a.n + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));                     // (`rows` is pageable memory; the call is a blocking one anyway)
+    for (int r : rows) {
+        int* sl = &c->trk_slots[(size_t)r * V];
+        int M = 0;
+        for (int v = 0; v < c->trk_M[r]; ++v) if (a.remap[sl[v]] >= 0) sl[M++] = a.remap[sl[v]];
+        c->trk_views -= c->trk_M[r] - M;
+        c->trk_M[r] = M;
+        if (c->trk_anchor[r] >= 0) c->trk_anchor[r] = a.remap[c->trk_anchor[r]];
+        if (M == 0) { c->trk_dropped.push_back(c->trk_id[r]); tracks_free_row(c, r); }
+    }
+    return MSCKF_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 const char* msckf_strerror(int code) {
@@ -2268,7 +2415,7 @@ void msckf_destroy(msckf_ctx* c) {
                   &c->dLineBase, &c->dLineDir, &c->dLineConf, &c->dLostFor, &c->dTrackedFor, &c->dSelFlags, &c->dWorld,
                   &c->dFlush, &c->dFlushOff, &c->dFeatInfo, &c->dCommBuf, &c->dAssocUV, &c->dAssocRes,
                   &c->dGsEx, &c->dGsFlag, &c->dGsProg, &c->dMProg, &c->dMFlush, &c->dRootFlush, &c->dXRootFlush,
-                  &c->dSplit, &c->dRem, &c->dNom};
+                  &c->dSplit, &c->dRem, &c->dNom, &c->dTrk, &c->dTrkRows, &c->dTrkRowSorted};
     for (Buf* b : all) if (b->p && !b->view) (void)hipFree(b->p);
     for (Buf* b : {&c->dPoseArena, &c->dFeatArena, &c->dRawArena, &c->dResArena, &c->dGateArena, &c->dPlanArena}) if (b->p) (void)hipFree(b->p);
     for (void* h : {c->hPose, c->hFeat, c->hRes, c->hGate, c->hP}) if (h) (void)hipHostFree(h);
@@ -2282,6 +2429,10 @@ void msckf_destroy(msckf_ctx* c) {
     if (c->hPlan) (void)hipHostFree(c->hPlan);
     if (c->ev_state) (void)hipEventDestroy(c->ev_state);
     if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
+    for (PinStage* ps : {&c->trk_obs_stage, &c->trk_load_stage}) {
+        if (ps->ev) (void)hipEventDestroy(ps->ev);
+        if (ps->p) (void)hipHostFree(ps->p);
+    }
     if (c->stream_up) (void)hipStreamDestroy(c->stream_up);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2322,15 +2473,18 @@ int msckf_set_state(msckf_ctx* c, int32_t N, const double* P, const double* cam_
     c->us_h2d = (float)(now_us() - t0);
     c->have_state = true;
     c->ran = false;
+    tracks_clear(c);                      // clone slots lose their meaning
     return MSCKF_OK;
 }
 
-int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const double* obs_uv,
-                       const int32_t* obs_slot, const double* idp_base, const double* idp_m,
-                       const double* idp_rho) {
+// The batch upload.  Validation of the integers, the sort and the K5 plan are the same whoever supplies the floats: the caller
+// (msckf_set_features: staged through the pinned image) or the track store (emit != nullptr: written in HBM by k_track_emit).
+static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const double* obs_uv,
+                             const int32_t* obs_slot, const double* idp_base, const double* idp_m,
+                             const double* idp_rho, const TrackEmitSrc* emit) {
     if (!c || F < 0 || F > c->maxF) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
-    if (F > 0 && (!view_ptr || !obs_uv || !obs_slot || !idp_base || !idp_m || !idp_rho)) return MSCKF_ERR_ARG;
+    if (F > 0 && (!view_ptr || !obs_slot || (!emit && (!obs_uv || !idp_base || !idp_m || !idp_rho)))) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     const double t0 = now_us();
     const int N = c->N;
@@ -2342,6 +2496,7 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
     c->ran = false;
     c->have_tracks = false;
     c->use_select = false;
+    c->batch_from_store = false;
     c->no_wide = false;
     if (F == 0) {
         c->F = 0;
@@ -2408,8 +2563,10 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
     char* hb = static_cast<char*>(c->hFeat);
     char* draw = static_cast<char*>(c->dRawArena.p);
     const bool par = c->pool && F >= host_par_min();
-    if (par) c->pool->copy(hb + r_uv, obs_uv, (size_t)sumM * 16); else std::memcpy(hb + r_uv, obs_uv, (size_t)sumM * 16);
-    HIPCHK(c, hipMemcpyAsync(draw, hb + r_uv, (size_t)sumM * 16, hipMemcpyHostToDevice, c->stream));
+    if (!emit) {
+        if (par) c->pool->copy(hb + r_uv, obs_uv, (size_t)sumM * 16); else std::memcpy(hb + r_uv, obs_uv, (size_t)sumM * 16);
+        HIPCHK(c, hipMemcpyAsync(draw, hb + r_uv, (size_t)sumM * 16, hipMemcpyHostToDevice, c->stream));
+    }
     // (the one-shot call's state went up on the side stream: the main stream learns of it HERE, behind a copy it has to wait for
     //  anyway -- between k_gather and k_feature the cross-stream wait cost ~4 us of an otherwise back-to-back pair)
     if (c->state_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_state, 0)); c->state_pending = false; }
@@ -2430,10 +2587,12 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
         auto validate = [&](int ch) {
             const int f0 = (int)((long long)F * ch / nch), f1 = (int)((long long)F * (ch + 1) / nch);
             const int a0 = view_ptr[f0], a1 = view_ptr[f1];
-            std::memcpy(hb + r_slot + (size_t)a0 * 4, obs_slot + a0, (size_t)(a1 - a0) * 4);
-            std::memcpy(hb + r_base + (size_t)f0 * 24, idp_base + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
-            std::memcpy(hb + r_m + (size_t)f0 * 24, idp_m + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
-            std::memcpy(hb + r_rho + (size_t)f0 * 8, idp_rho + f0, (size_t)(f1 - f0) * 8);
+            if (!emit) {
+                std::memcpy(hb + r_slot + (size_t)a0 * 4, obs_slot + a0, (size_t)(a1 - a0) * 4);
+                std::memcpy(hb + r_base + (size_t)f0 * 24, idp_base + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
+                std::memcpy(hb + r_m + (size_t)f0 * 24, idp_m + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
+                std::memcpy(hb + r_rho + (size_t)f0 * 8, idp_rho + f0, (size_t)(f1 - f0) * 8);
+            }
             int mm[3] = {0, 0, 0}, nmid = 0, nlong = 0;
             for (int f = f0; f < f1; ++f) {
                 const int a = view_ptr[f], b = view_ptr[f + 1], M = b - a;
@@ -2480,7 +2639,9 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
         for (int f = 0; f < F; ++f) key_in[f] = (int)((size_t)key_in[f] % NN);
         Mmax_cls[0] = Mmax; Mmax_cls[2] = 0;
     }
-    if (!zc) HIPCHK(c, hipMemcpyAsync(draw + r_base, hb + r_base, raw_bytes - r_base, hipMemcpyHostToDevice, c->stream));
+    if (emit) {
+        // (the store's floats never visit the host: k_track_emit lays the raw image down in front of k_gather, below)
+    } else if (!zc) HIPCHK(c, hipMemcpyAsync(draw + r_base, hb + r_base, raw_bytes - r_base, hipMemcpyHostToDevice, c->stream));
     else {
         const size_t n16 = (raw_bytes - r_base) / 16;           // (r_base and raw_bytes are multiples of 16)
         hipLaunchKernelGGL(k_stage, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, c->stream,
@@ -2648,6 +2809,9 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
     if (!zc) HIPCHK(c, hipMemcpyAsync(draw + raw_bytes, hb + raw_bytes, (size_t)Fs * sizeof(GatherRec), hipMemcpyHostToDevice, c->stream));
     if (c->split_on) HIPCHK(c, hipMemcpyAsync(c->dSplit.p, hb + split_off, c->h_split.size() * sizeof(SplitRec), hipMemcpyHostToDevice, c->stream));
     if (c->oneshot) HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
+    if (emit) {
+        if (int rce = launch_track_emit(c, emit, F, sumM, view_ptr, h_view, draw, r_base, r_m, r_rho, r_slot)) return rce;
+    }
     {
         GatherArgs g;
         g.uv_in = reinterpret_cast<const double*>(draw);
@@ -2713,6 +2877,12 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
     c->hp[1] += tv - t0; c->hp[2] += ts - tv; c->hp[3] += t1 - ts; c->hp[4] += t2 - t1; c->hp[5] += t3 - t2; c->hp[6] += now_us() - t3;
     c->have_features = true;
     return MSCKF_OK;
+}
+
+int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const double* obs_uv,
+                       const int32_t* obs_slot, const double* idp_base, const double* idp_m,
+                       const double* idp_rho) {
+    return set_features_impl(c, F, view_ptr, obs_uv, obs_slot, idp_base, idp_m, idp_rho, nullptr);
 }
 
 int msckf_run(msckf_ctx* c) {
@@ -3081,6 +3251,10 @@ int msckf_run_select(msckf_ctx* c, const msckf_select_params* sp) {
     a.flags = ptr<unsigned char>(c->dSelFlags); a.idp_m = ptr<double>(c->dMvec); a.idp_rho = ptr<double>(c->dRho);
     a.world = ptr<double>(c->dWorld);
     hipLaunchKernelGGL(k_select, dim3((c->F * 8 + 255) / 256), dim3(256), 0, c->stream, a);
+    if (c->batch_from_store)                                // the reference's refresh persists (MSCKF.py:488)
+        hipLaunchKernelGGL(k_track_writeback, dim3((c->F + 255) / 256), dim3(256), 0, c->stream, c->trk, c->F,
+                           (const unsigned char*)a.flags, (const double*)a.idp_m, (const double*)a.idp_rho,
+                           (const int*)ptr<int>(c->dTrkRowSorted));
     HIPCHK(c, hipGetLastError());
     return MSCKF_OK;
 }
@@ -3284,6 +3458,7 @@ int msckf_remove_clones(msckf_ctx* c, int32_t n, const int32_t* slots) {
         }
     }
     const int nn = (int)keep.size();
+    if (int rct = tracks_drop_clones(c, drop)) return rct;       // (reads the positions of the clones that go: before the poses move)
     HIPCHK(c, hipMemcpyAsync(c->dKeep.p, keep.data(), (size_t)nn * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_compact, dim3((nn * nn + 255) / 256), dim3(256), 0, c->stream, ptr<double>(c->dP), c->d,
                        ptr<int>(c->dKeep), nn, ptr<double>(c->dB2));
@@ -3424,6 +3599,152 @@ int msckf_commit_inject(msckf_ctx* c) {
     HIPCHK(c, hipGetLastError());
     c->main_busy = true;
     return MSCKF_OK;
+}
+
+// ---- the track store: views and bases in HBM, batches by track id (k_tracks.h) -----------------------------------
+int msckf_tracks_reset(msckf_ctx* c) {
+    if (!c) return MSCKF_ERR_ARG;
+    tracks_clear(c);
+    return MSCKF_OK;
+}
+
+int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const double* uv, const double* score) {
+    if (!c || n < 0) return MSCKF_ERR_ARG;
+    if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
+    if (n == 0) return MSCKF_OK;
+    if (!ids || !uv || !score) return MSCKF_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = tracks_ensure(c)) return rc;
+    const int newest = c->N - 1, V = c->maxM;
+    // every check first: an erroring call leaves the store exactly as it was
+    {
+        std::unordered_set<int> seen;
+        size_t fresh = 0;
+        for (int i = 0; i < n; ++i) {
+            if (ids[i] < 0) return MSCKF_ERR_ARG;
+            if (!seen.insert(ids[i]).second) return MSCKF_ERR_DUP_SLOT;
+            const auto it = c->trk_row_of.find(ids[i]);
+            if (it == c->trk_row_of.end()) { ++fresh; continue; }
+            const int r = it->second, M = c->trk_M[r];
+            if (M > 0 && c->trk_slots[(size_t)r * V + M - 1] == newest) return MSCKF_ERR_DUP_SLOT;
+            if (M + 1 > V) return MSCKF_ERR_ARG;
+        }
+        if (fresh > c->trk_free.size()) return MSCKF_ERR_ARG;
+    }
+    if (int rc = stage_acquire(c, c->trk_obs_stage, (size_t)n * sizeof(TrackObsRec))) return rc;
+    TrackObsRec* rec = static_cast<TrackObsRec*>(c->trk_obs_stage.p);
+    for (int i = 0; i < n; ++i) {
+        const auto it = c->trk_row_of.find(ids[i]);
+        int r, fresh = 0;
+        if (it == c->trk_row_of.end()) {
+            r = c->trk_free.back(); c->trk_free.pop_back();
+            c->trk_row_of.emplace(ids[i], r);
+            c->trk_id[r] = ids[i]; c->trk_M[r] = 0; c->trk_anchor[r] = newest;
+            fresh = 1;
+        } else r = it->second;
+        const int pos = c->trk_M[r]++;
+        c->trk_slots[(size_t)r * V + pos] = newest;
+        ++c->trk_views;
+        rec[i] = TrackObsRec{r, pos, fresh, 0, uv[2 * i], uv[2 * i + 1], score[i]};
+    }
+    TrackObsArgs a{};
+    a.s = c->trk; a.rec = rec; a.n = n; a.slot = newest;
+    a.R = ptr<double>(c->dCamR) + 9 * (size_t)newest;
+    std::memcpy(a.Kinv, c->Kinv, sizeof(a.Kinv));
+    hipLaunchKernelGGL(k_track_observe, dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    c->main_busy = true;
+    return stage_release(c, c->trk_obs_stage);
+}
+
+int msckf_tracks_remove(msckf_ctx* c, int32_t n, const int32_t* ids) {
+    if (!c || n < 0 || (n > 0 && !ids)) return MSCKF_ERR_ARG;
+    std::unordered_set<int> seen;
+    for (int i = 0; i < n; ++i)
+        if (!c->trk_row_of.count(ids[i]) || !seen.insert(ids[i]).second) return MSCKF_ERR_ARG;
+    for (int i = 0; i < n; ++i) tracks_free_row(c, c->trk_row_of[ids[i]]);
+    return MSCKF_OK;
+}
+
+int msckf_tracks_load(msckf_ctx* c, int32_t F, const int32_t* ids, const int32_t* lost_for, const int32_t* tracked_for) {
+    if (!c || F < 0 || F > c->maxF) return MSCKF_ERR_ARG;
+    if (!c->have_state) return MSCKF_ERR_STATE;
+    if (F > 0 && (!ids || !lost_for || !tracked_for)) return MSCKF_ERR_ARG;
+    const int V = c->maxM;
+    std::vector<int> rows(F), view_ptr(F + 1, 0), slots;
+    {
+        std::unordered_set<int> seen;
+        for (int f = 0; f < F; ++f) {
+            const auto it = c->trk_row_of.find(ids[f]);
+            if (it == c->trk_row_of.end() || !seen.insert(ids[f]).second) return MSCKF_ERR_ARG;
+            rows[f] = it->second;
+            view_ptr[f + 1] = view_ptr[f] + c->trk_M[rows[f]];
+        }
+    }
+    slots.resize(view_ptr[F]);
+    for (int f = 0; f < F; ++f)
+        std::memcpy(slots.data() + view_ptr[f], &c->trk_slots[(size_t)rows[f] * V], (size_t)c->trk_M[rows[f]] * 4);
+    const TrackEmitSrc src{rows.data(), lost_for, tracked_for};
+    const int rc = set_features_impl(c, F, view_ptr.data(), nullptr, slots.data(), nullptr, nullptr, nullptr, &src);
+    if (rc != MSCKF_OK) return rc;
+    c->have_tracks = true;                // the lines and counters went with the batch (msckf_set_tracks' half)
+    c->batch_from_store = F > 0;
+    return MSCKF_OK;
+}
+
+int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, double* uv, double* dir, double* conf,
+                     double* line_base, double* idp_base, double* idp_m, double* idp_rho, int32_t* anchor_slot) {
+    if (!c) return MSCKF_ERR_ARG;
+    const auto it = c->trk_row_of.find(id);
+    if (it == c->trk_row_of.end()) return MSCKF_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t r = it->second, V = c->maxM, N = c->N;
+    const int M = c->trk_M[r];
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const TrackStore& s = c->trk;
+    std::vector<int> sl(V);
+    std::vector<double> huv(2 * V), hdir(3 * V), hconf(V), camt(3 * std::max<size_t>(N, 1));
+    double m[3], rho, frozen[3];
+    int anchor = 0, count = 0;
+    HIPCHK(c, hipMemcpy(sl.data(), s.slot + r * V, V * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(huv.data(), s.uv + 2 * r * V, V * 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hdir.data(), s.dir + 3 * r * V, V * 24, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hconf.data(), s.conf + r * V, V * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(m, s.m + 3 * r, 24, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&rho, s.rho + r, 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(frozen, s.frozen + 3 * r, 24, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&anchor, s.anchor + r, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&count, s.count + r, 4, hipMemcpyDeviceToHost));
+    if (N > 0) HIPCHK(c, hipMemcpy(camt.data(), c->dCamT.p, N * 24, hipMemcpyDeviceToHost));
+    // the integers are the device's; the mirror must agree with them
+    bool same = count == M && anchor == c->trk_anchor[r] && anchor < (int)N;
+    for (int v = 0; same && v < M; ++v) same = sl[v] == c->trk_slots[r * V + v] && sl[v] >= 0 && sl[v] < (int)N;
+    if (!same) { c->last_error = "track store: the device rows and the host mirror differ"; return MSCKF_ERR_STATE; }
+    if (M_out) *M_out = M;
+    if (slots) std::memcpy(slots, sl.data(), (size_t)M * 4);
+    if (uv) std::memcpy(uv, huv.data(), (size_t)M * 16);
+    if (dir) std::memcpy(dir, hdir.data(), (size_t)M * 24);
+    if (conf) std::memcpy(conf, hconf.data(), (size_t)M * 8);
+    if (line_base) for (int v = 0; v < M; ++v) std::memcpy(line_base + 3 * v, &camt[3 * (size_t)sl[v]], 24);
+    if (idp_base) std::memcpy(idp_base, anchor >= 0 ? &camt[3 * (size_t)anchor] : frozen, 24);
+    if (idp_m) std::memcpy(idp_m, m, 24);
+    if (idp_rho) *idp_rho = rho;
+    if (anchor_slot) *anchor_slot = anchor;
+    return MSCKF_OK;
+}
+
+int msckf_tracks_count(msckf_ctx* c, int32_t* n_tracks, int32_t* n_views) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (n_tracks) *n_tracks = (int32_t)c->trk_row_of.size();
+    if (n_views) *n_views = (int32_t)c->trk_views;
+    return MSCKF_OK;
+}
+
+int msckf_tracks_dropped(msckf_ctx* c, int32_t* ids, int32_t cap) {
+    if (!c || cap < 0 || (cap > 0 && !ids)) return MSCKF_ERR_ARG;
+    const int n = (int)c->trk_dropped.size();
+    if (n > 0 && cap > 0) std::memcpy(ids, c->trk_dropped.data(), (size_t)std::min(n, (int)cap) * 4);
+    return n;
 }
 
 size_t msckf_block_doubles(const msckf_ctx* c) { return c ? (size_t)c->dc * (c->dc + 1) : 0; }

@@ -11,7 +11,13 @@ Timed: everything of a frame except `set_features ... result` (the update is the
 the end of each timed stretch.  Both loops run in one process on engines of one size, interleaved run by run after one
 untimed run each.  `--samples 20` splits every sample's dt in five (4 -> 20 samples per frame).
 
-    python tools/frame_loop.py [--samples 4|20] [--runs 7] [--loop a|b|both] [--out FILE]"""
+  (c) the batch hand-over of a frame on top of loop (b), timed on its own (`--loop c`): what it takes to put a call's
+      candidates in front of `run_select`, up to a stream sync.  Parent side: `nominal()` (the bases live on the device
+      after an injection), the bases resolved on the host, `set_features`, `set_tracks`.  New side: `tracks_observe` +
+      `load_tracks` on the resident track store (`tests/track_events.py` supplies the frame's keypoints).  The update
+      itself stays outside the timed stretch; both sides interleaved run by run in one process.
+
+    python tools/frame_loop.py [--samples 4|20] [--runs 7] [--loop a|b|both|c] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -113,13 +119,105 @@ def drive(run, eng, frames, loop):
     return out
 
 
+def drive_handover(run, eng, frames, events, side):
+    """Loop (b) with the batch hand-over timed: side "host" = nominal() + host bases + set_features + set_tracks,
+    side "store" = tracks_observe + load_tracks.  Returns the timed seconds of every selection call."""
+    z = run.z
+    params = run.select_params()
+    eng.set_prior(z["P0"], z["gravity"], z["K"], run.sigma)
+    eng.set_nominal(z["imu_R0"][0], z["imu_t0"][0], z["imu_v0"][0], z["gravity"], z["Qc"],
+                    T_W_I=(z["T_W_I_R"], z["T_W_I_t"]), T_W_C=(z["T_W_C_R"], z["T_W_C_t"]))
+    clock = time.perf_counter
+    out, keys, anchor_key, frozen = [], [], {}, {}
+    for fr in frames:
+        sm = fr["samples"]
+        eng.propagate_imu(np.array([s["gyro_raw"] for s in sm]), np.array([s["acc_raw"] for s in sm]), np.array([s["dt"] for s in sm]))
+        for kind, idx in fr["ops"]:
+            if kind == AUGMENT:
+                eng.augment_imu()
+                keys.append(int(run.aug(idx)["key"]))
+            elif kind in (PROCESS, PRUNE):
+                c, ev = run.call(idx), events[idx]
+                N = eng.n_clones
+                pool = ev["observe_pool"]
+                uv, score = z["pool_uv"][pool].astype(np.float64), z["pool_score"][pool].astype(np.float64)
+                for i in ev["observe_ids"].tolist():
+                    anchor_key.setdefault(i, keys[-1])
+                slot_of = {k: s for s, k in enumerate(keys)}
+                anchors = [slot_of.get(anchor_key[i], -1) for i in c["ids"].tolist()]
+                eng.sync()
+                t0 = clock()
+                if side == "host":
+                    cam_t = eng.nominal()["cam_t"]
+                    idp_base = np.array([cam_t[a] if a >= 0 else frozen[i] for a, i in zip(anchors, c["ids"].tolist())]).reshape(-1, 3)
+                    c = dict(c, line_base=cam_t[c["obs_slot"]], idp_base=idp_base)
+                    prob = run.problem(c, np.zeros((15 + 6 * N,) * 2), np.zeros((N, 3, 3)), np.zeros((N, 3)))
+                    eng.set_features(prob)
+                    eng.set_tracks(run.tracks(c))
+                else:
+                    eng.tracks_observe(ev["observe_ids"], uv, score)
+                    eng.load_tracks(c["ids"], c["lost"], c["tracked"])
+                eng.sync()
+                out.append(clock() - t0)
+                eng.run_select(params, z["K"])
+                if int(eng.selection().valid.sum()):
+                    eng.run()
+                    eng.result()
+                    eng.commit_inject()
+                if side == "store":
+                    eng.tracks_remove(ev["remove"])
+                if len(ev["rm"]):
+                    before = eng.nominal()["cam_t"]
+                    for i, k in anchor_key.items():
+                        if k in [keys[s] for s in ev["rm"]] and i not in frozen:
+                            frozen[i] = before[slot_of[k]].copy()
+                    eng.remove_clones(ev["rm"])
+                    keys = [k for s, k in enumerate(keys) if s not in ev["rm"]]
+            elif kind == REMOVE:
+                raise RuntimeError("the run holds no REMOVE op")
+    return out
+
+
+def main_handover(args):
+    import track_events
+    from msckf_amd.api import UpdateEngine
+    run = window30.Run()
+    frames, events = frames_of(run, args.samples // 4), track_events.derive(run)
+    sides = ["host", "store"]
+    engines = {sd: UpdateEngine(max_clones=31, max_features=4096, max_track=31) for sd in sides}
+    per_run = {sd: [] for sd in sides}
+    for sd in sides:
+        drive_handover(run, engines[sd], frames, events, sd)        # warm-up
+    for _ in range(args.runs):
+        for sd in sides:
+            per_run[sd].append(drive_handover(run, engines[sd], frames, events, sd))
+    lines = [f"(c) batch hand-over of a selection call, {len(per_run['host'][0])} calls of at most 138 tracks, {args.runs} runs; us per call"]
+    names = {"host": "nominal() + host bases + set_features + set_tracks", "store": "tracks_observe + load_tracks"}
+    for sd in sides:
+        t = np.array(per_run[sd]) * 1e6
+        meds = np.median(t, axis=1)
+        lines.append(f"  {names[sd]:52s} median {np.median(t):8.1f}   p10 {np.percentile(t, 10):8.1f}   p90 {np.percentile(t, 90):8.1f}   "
+                     f"medians of the runs: min {meds.min():8.1f}  max {meds.max():8.1f}")
+    mh, ms = (np.median(np.array(per_run[sd]) * 1e6, axis=1) for sd in sides)
+    lines.append(f"  host / store of the runs' medians: {np.median(mh) / np.median(ms):.2f}x")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+    for e in engines.values():
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samples", type=int, default=4, choices=(4, 20))
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--loop", default="both", choices=("a", "b", "both"))
+    ap.add_argument("--loop", default="both", choices=("a", "b", "both", "c"))
     ap.add_argument("--out")
     args = ap.parse_args()
+    if args.loop == "c":
+        return main_handover(args)
     from msckf_amd.api import UpdateEngine
     run = window30.Run()
     frames = frames_of(run, args.samples // 4)

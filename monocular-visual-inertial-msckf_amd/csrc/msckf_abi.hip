@@ -38,6 +38,7 @@
 #include "k_nominal.h"
 #include "k_assoc.h"
 #include "k_tracks.h"
+#include "run_outcome.h"
 
 using namespace msckf;
 
@@ -257,6 +258,26 @@ inline int host_par_min() {
     return v;
 }
 
+// What a run launched: everything a reader of its results needs to know.  The launchers (run_pipeline, msckf_run_merge_gain,
+// run_merge_groups) fill a local one and commit it with finish_run when every launch is in the stream; a run that returns an
+// error commits nothing.
+enum class RunKind { Pipeline, RootMerge, GroupMerge };
+enum class AccSource { Gate, Fixed, Word2 };     // the accepted count: the gate results' sum, `accepted`, status word 2 (summed on the device)
+struct RunRecord {
+    bool ran = false;                     // a run was committed and nothing has voided its results since
+    RunKind kind = RunKind::Pipeline;
+    bool gain = false;                    // K6-K7 ran
+    bool word1_ours = false;              // a launch of the run wrote status word 1 (an early update, a chain, the blocked Cholesky's second block)
+    bool word4_ours = false;              // ... status word 4 (a merge of split records)
+    AccSource acc = AccSource::Gate;
+    int accepted = 0;
+    bool direct = false;                  // K6-K7 mirrored status | dx | P+ into hRes
+    bool streamed_gain = false;           // pipeline: K6-K7 was k_gain_stream (fused or a launch of its own)
+    bool fused_root = false;              // pipeline: ... in the root sweep's launch (k_root_gain: stage events cannot split it)
+    bool fused_leaves = false;            // pipeline: ... and the leaves with them (k_leaf_root_gain)
+    long serial = 0;                      // finish_run numbers the runs
+};
+
 }  // namespace
 
 struct msckf_ctx {
@@ -271,12 +292,11 @@ struct msckf_ctx {
     int maxN = 0, maxF = 0, maxM = 0;
     // current problem
     int N = 0, d = 0, dc = 0, F = 0, sumM = 0, Mmax = 0;
-    bool have_state = false, have_features = false, ran = false, ran_gain = false;
-    bool acc_from_dev = false;            // the accepted total of a merged update sits in status word 2 (summed on the device)
+    bool have_state = false, have_features = false;
+    RunRecord last;                       // the last run (finish_run)
     ncclComm_t comm = nullptr;            // RCCL communicator of the sharded update (msckf_comm_init)
     int comm_rank = 0, comm_world = 1;
     Buf dCommBuf;
-    bool gain_blocked = false;            // the last K6 ran the two-block factorisation (second status word in use)
     double sigma = 0.0;
     double g[3]{}, Kinv[9]{};
     int n_chi2 = 0;
@@ -312,8 +332,8 @@ struct msckf_ctx {
     bool plan_xchg = false;
     std::vector<int> plan_fmin, plan_fmax, plan_view;
     long long stack_elems = 0;            // scalars of the current batch's stack blocks (a zero word follows them)
-    int leaf_nf = 8;
-    bool leaf_tall = false;               // 90-column leaves with 56-row blocks (k_lsweep<8, 6, LS_RS6T>)                      // row blocks in flight per 60-column leaf workgroup (8 or 12)
+    int leaf_nf = 8;                      // row blocks in flight per 60-column leaf workgroup (8 or 12)
+    bool leaf_tall = false;               // 90-column leaves with 56-row blocks (k_lsweep<8, 6, LS_RS6T>)
     bool leaf_narrow = false, leaf_wide = false;      // band plan: leaf nodes with w + 1 <= 64 / > 64 exist
     size_t root_off = 0;                  // offset (doubles) of the root block [T | r_n] in rbuf
     size_t zero_off = 0;                  // 16 doubles of the workspace no kernel writes: they read 0.0
@@ -325,10 +345,6 @@ struct msckf_ctx {
     // record carries a remainder section [count word | xsplit_rows rows of 6N + 1 doubles] (the rows of its accepted long tracks)
     int xsplit_rows = 0;                  // rows one record's remainder section holds (0: off, records as before)
     int xsplit_total = 0;                 // bound on the remainder rows of the whole batch (the merge's second source of rows)
-    bool x_rem_merge = false;             // the merge being launched carries split records: K6-K7 has TWO sources of rows
-    int x_rem_blocks = 0;                 // ... row blocks of 16 the merge's dense rows may fill (dRem)
-    bool x_rem_last = false;              // the last run was such a merge (status word 4 is its)
-    bool x_status1 = false;               // status word 1 was written by a launch of the last run or merge (an early update or a chain)
     std::vector<double> h_xflags;         // [N] 1.0 where this shard has tracks starting at the slot
     std::vector<double> x_key;            // flags of the last merged records (plan cache of msckf_run_merge_groups)
     int x_nrec = 0;
@@ -343,7 +359,6 @@ struct msckf_ctx {
     int gather_cap = 0;
     int n_leaves = 0;
     int n_leaves0 = 0;                    // band plan: the leaves [0, n_leaves0) fold short tracks only (none of a split track's blocks)
-    int acc_override = -1;                // total accepted over all shards (merge_gain path)
     float us_host_prep = 0, us_h2d = 0, us_d2h = 0;
     float us_stage[3] = {0, 0, 0};
     float us_total = 0;
@@ -382,8 +397,6 @@ struct msckf_ctx {
     bool gs_overlap = true;               // MSCKF_GAIN_OVERLAP=0: k_gain_stream as a launch of its own behind the root sweep
     int root_band = 0;                    // widest row of the root block in columns (the local plan's / the merge plan's)
     bool gs_stamp = false;                // msckf_run_timed: k_root_gain notes when its sweep ends and when its update ends
-    bool gs_fused_last = false;           // the last pipeline ran k_root_gain (stage events cannot split it)
-    bool gs_last = false;                 // the last pipeline's K6-K7 was k_gain_stream (fused or a launch of its own)
     // tracks that span more than WIDE_SPAN clone slots are sorted behind the others ([0, Fb) short, [Fb, F) long) and split
     int Fb = 0, Fw = 0, Fw1 = 0, Mmax_band = 0, Mmax_wide = 0, Mmax_w1 = 0;   // (Fw1 of the Fw wide tracks have <= 15 views)
     // Round 5: a long track (more than WIDE_SPAN clone slots) is SPLIT (k_feature.h, two-level nullspace basis): the sorted
@@ -404,10 +417,6 @@ struct msckf_ctx {
     static constexpr int REM_DIRECT_DEFAULT = 3840;
     int rem_leaf_rows = 0;                // rows of a leaf of the remainder rows' merge tree (MSCKF_REM_LEAF_ROWS; 0: one register batch of k_fold)
     int rem_direct_max = REM_DIRECT_DEFAULT, rem_direct_max_wide = 16 * GS_MAX_NB2;
-    bool in_merge = false;                // a merge of gathered shard blocks is being launched: its K6-K7 has ONE source of rows, whatever the
-                                          //   rank's own last batch looked like
-    bool t2_early = false;                // this run: the dense remainder rows were applied by a launch of their own (launch_gain_t2_early); the update
-                                          //   on the band root starts from that launch's P_out / dx
     bool retry_plain = false;             // a K6-K7 launch timed out once: the context runs without in-launch waits since (msckf_get_result)
     bool fake_timeout_done = false;       // MSCKF_DEBUG_FAKE_TIMEOUT
     bool rem_direct = false;              // ... few enough (3840; 16384 on windows of more than 31 clones): K6-K7 takes them as they are (k_rem_scatter), no QR of their own
@@ -445,8 +454,6 @@ struct msckf_ctx {
     // them waits behind its predecessor) are gone, the host reads hGate / hRes when the stream has drained.
     bool want_direct = false;             // msckf_update is running (and MSCKF_DIRECT_RESULT is not 0)
     bool gate_direct = false;             // this batch's k_feature mirrored its results into hGate
-    bool res_direct = false;              // this run's K6-K7 mirrored status | dx | P+ into hRes
-    long direct_serial = -1;              // ... the run it did so for (run_serial)
     // ... and the gate results are on the host when K1-K4 have ended (ev_gate): msckf_update sums them and fills the caller's mask
     // while K5-K7 run, msckf_get_result finds the sums here
     hipEvent_t ev_gate = nullptr;
@@ -455,8 +462,6 @@ struct msckf_ctx {
     int gate_cnt[4] = {0, 0, 0, 0};
     const uint8_t* gate_mask_dst = nullptr;
     bool direct_enabled = true;
-    // Resident calls that leave their work in the stream without waiting for it (msckf_set_features, msckf_set_poses,
-    // msckf_commit_covariance): the next call that rewrites a pinned staging buffer, or that uses the side stream, waits first.
     // The last level of group merges inside k_root_gain's launch, the root taking their rows as they are published (k_gstream.h):
     bool root_streamed = false;           // this plan's root folds name their producers (SweepFold::prod), first fold not adopted
     int stream_level = -1;                // index of that level in sweep_levels
@@ -471,7 +476,6 @@ struct msckf_ctx {
     bool leaf_stream_enabled = true;      // MSCKF_LEAF_STREAM=0: the leaves keep their own launch (A/B)
     bool leaf_fused = false;              // this plan's merge level and root name the leaves as producers (SweepFold::prod)
     bool leaf_ld64 = false;               // the leaves' output rows are 64 doubles (streamable)
-    bool leaves_fused_last = false;       // the last pipeline ran k_leaf_root_gain
     int n_cu = 256;                       // compute units of the device: workgroups that wait for each other inside one launch must all be resident
     bool feat_busy = false, pose_busy = false;   // hFeat / hPose may still be read by a copy or by k_gather
     bool main_busy = false;                      // the main stream holds work nobody has waited for
@@ -489,7 +493,6 @@ struct msckf_ctx {
     long long trk_views = 0;
     bool batch_from_store = false;        // the current batch came through msckf_tracks_load: msckf_run_select writes refreshed points back
     PinStage trk_obs_stage, trk_load_stage;
-    long run_serial = 0;                  // bumped by every pipeline / merge launch
     long fetched_serial = -1;             // the run whose return code msckf_get_result derived last ...
     int fetched_rc = 0;                   // ... and that code: msckf_commit_covariance need not read the gate results again
 };
@@ -608,7 +611,7 @@ void invalidate_batch(msckf_ctx* c) {
     c->have_features = false;
     c->have_tracks = false;
     c->use_select = false;
-    c->ran = false;
+    c->last.ran = false;
     c->F = 0;
     c->batch_from_store = false;
 }
@@ -1424,10 +1427,8 @@ int upload_plan(msckf_ctx* c) {
 // the export record when the batch is planned with split records
 inline bool rem_in_record(const msckf_ctx* c) { return c->xchg_planned && c->xsplit_rows > 0; }
 inline double* rem_rows(msckf_ctx* c) { return rem_in_record(c) ? ptr<double>(c->dRbuf) + rec_rem_off(c) + 1 : ptr<double>(c->dRem); }
-inline int* rem_count(msckf_ctx* c) {
-    return rem_in_record(c) ? reinterpret_cast<int*>(ptr<double>(c->dRbuf) + rec_rem_off(c))
-                            : reinterpret_cast<int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1));   // behind the matrix
-}
+inline int* drem_count(msckf_ctx* c) { return reinterpret_cast<int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1)); }   // behind the matrix
+inline int* rem_count(msckf_ctx* c) { return rem_in_record(c) ? reinterpret_cast<int*>(ptr<double>(c->dRbuf) + rec_rem_off(c)) : drem_count(c); }
 
 int launch_feature(msckf_ctx* c) {
     if (c->F == 0) return MSCKF_OK;
@@ -1594,6 +1595,12 @@ int launch_solve_regs(msckf_ctx* c, int nreg, const SolveArgs& a) {
     return MSCKF_OK;
 }
 
+// Round 3's K6 factors a window wider than one register-tiled Cholesky in two blocks, the second block's status in word 1 -- where
+// it runs at all: the streamed K6-K7 (k_gain_stream, dtype f64 too) takes every window of up to GS_MAX_NS strips and uses word 0 only.
+inline bool gain_is_blocked(bool gs_enabled, int dc) {
+    return !(gs_enabled && (dc + 15) / 16 + 1 <= GS_MAX_NS) && dc > 4 * CHOL_TILE_MAX_NT && dc <= 2 * GAIN_BLK && dc - GAIN_BLK >= 4;
+}
+
 // K6-K7 from the root block [T | r_n] (dc x (dc+1), row-major) and the prior P.
 int launch_gain(msckf_ctx* c, const double* Tblk) {
     const int d = c->d, dc = c->dc, ldt = dc + 1;
@@ -1609,8 +1616,7 @@ int launch_gain(msckf_ctx* c, const double* Tblk) {
     gemm(c, P + 15, d, Tblk, ldt, nullptr, 0, Y, dc, d, dc, dc, 1.0, 0.0, 0.0, 1, 1);
     // S = T Y[15:, :] + sigma^2 I            (MSCKF.py:605)
     gemm(c, Tblk, ldt, Y + (size_t)15 * dc, dc, nullptr, 0, S, dc, dc, dc, dc, 1.0, 0.0, s2, 0, 2);
-    c->gain_blocked = dc > 4 * CHOL_TILE_MAX_NT && dc <= 2 * GAIN_BLK && dc - GAIN_BLK >= 4;
-    if (c->gain_blocked) {
+    if (gain_is_blocked(false, dc)) {           // (this chain is running: the streamed update is not)
         if (int rcb = launch_chol_solve_blocked(c, S, Y, Kg, Tblk + dc, ldt)) return rcb;
     } else {
     // S = L L^T
@@ -1696,71 +1702,84 @@ bool gstream_ok(const msckf_ctx* c, int band) {
     const int ncb = c->wide_active ? nb : gstream_ncb(c->dc, band);      // (the remainder blocks' root is dense)
     return gstream_lds_doubles(ns, ncb) * 8 <= (size_t)(LDS_MAX_BYTES - 1024);
 }
-// Tblk: the root block [T | r_n]; band: its widest row in columns
-void fill_gstream_args(msckf_ctx* c, GStreamArgs& a, const double* Tblk, int band, bool beside) {
+// What one launch of the sequential block update works on: its sources of rows, where it starts, where it reports.
+struct GainSources {
+    const double* first = nullptr;        // the root block [T | r_n]; null: none
+    int band = 0;                         // ... its widest row in columns (dc where there is none)
+    const double* second = nullptr;       // dense rows [16 nb2][dc + 1], taken first; null: none
+    int nb2 = 0;                          // ... row blocks of 16 they may fill
+    const int* nb2_dev = nullptr;         // ... where their producer left the count of blocks; null: nb2 is the count
+    bool start_from_result = false;       // from P_out / dx, which an update on other rows of the batch left, not from the prior P
+    int status_word = 0;                  // 0: the run's main update; 1: a launch of its own ahead of it or behind it
+    void* mirror = nullptr;               // hRes: the main update mirrors status | dx | P+ there, a launch of its own its status word; null: none
+    bool two_sources_in_batch = false;    // the batch has a second source of rows, in this launch or another: no f32 update
+};
+void fill_gstream_args(msckf_ctx* c, GStreamArgs& a, const GainSources& s, bool beside) {
     const int d = c->d, dc = c->dc, nb = (dc + 15) / 16;
     a = GStreamArgs{};
-    a.P = ptr<double>(c->dP); a.ldp = d;
-    a.T = Tblk; a.ldt = dc + 1;
+    a.P = ptr<double>(s.start_from_result ? c->dPout : c->dP); a.ldp = d;
+    if (s.start_from_result) a.dx0 = ptr<double>(c->dDx);
+    a.T = s.first; a.ldt = dc + 1;
     a.progress = beside ? ptr<unsigned long long>(c->dGsProg) : nullptr;
     a.epoch = c->gs_epoch;
     a.ex = ptr<double>(c->dGsEx); a.exflag = ptr<unsigned long long>(c->dGsFlag);
     a.dx = ptr<double>(c->dDx); a.Pout = ptr<double>(c->dPout); a.ldo = d;
-    a.status = ptr<int>(c->dStatus);
-    const bool two = c->in_merge ? c->x_rem_merge : c->wide_active;
-    const bool early = c->t2_early && two;
-    if (c->res_direct && c->want_direct) {
-        char* h = static_cast<char*>(c->hRes);
+    a.status = ptr<int>(c->dStatus) + s.status_word;
+    if (s.mirror && s.status_word == 0) {
+        char* h = static_cast<char*>(s.mirror);
         a.status_h = reinterpret_cast<int*>(h); a.dx_h = reinterpret_cast<double*>(h + c->res_dx_off);
         a.Pout_h = reinterpret_cast<double*>(h + c->res_p_off);
-        // 3: not written.  (Word 1 is the early launch's mirror, seeded by launch_gain_t2_early: that launch is in flight by now.)
-        reinterpret_cast<int*>(h)[0] = 3; reinterpret_cast<int*>(h)[2] = 0;
-        if (!early) reinterpret_cast<int*>(h)[1] = 0;
+        // 3: not written.  (Behind an early launch word 1 is that launch's mirror, seeded below: it is in flight by now.)
+        a.status_h[0] = 3; a.status_h[2] = 0;
+        if (!s.start_from_result) a.status_h[1] = 0;
+    } else if (s.mirror) {                  // the direct result reads status word 1 from hRes: mirror it there
+        a.status_h = static_cast<int*>(s.mirror) + 1;
+        *a.status_h = 3;
     }
     a.sigma2 = c->sigma * c->sigma;
-    a.d = d; a.dc = dc; a.nb = nb; a.ns = nb + 1; a.ncb = gstream_ncb(dc, band);
-    a.nb1 = Tblk ? nb : 0;
+    a.d = d; a.dc = dc; a.nb = nb; a.ns = nb + 1; a.ncb = gstream_ncb(dc, s.band);
+    a.nb1 = s.first ? nb : 0;
     // (dtype = f32: the rank-16 products of the P-update on the f32 matrix cores -- but not for a batch with split long tracks: its
     //  dense remainder rows add tens of row blocks, every one an fp32-rounded product against a covariance that keeps shrinking;
     //  tools/soak_holes.py 150 8 f32, (48, 370, <= 22 views): dx off by 2.5e-4 with them, against the mode's 1e-4)
-    //  (a merge has ONE source of rows, whatever the rank's own last batch looked like -- unless it carries split records: their
-    //  remainder rows, collected into dRem by k_rem_collect, are its second)
-    a.f32_update = (c->cfg.dtype == MSCKF_DTYPE_F32 && !two) ? 1 : 0;
-    if (c->in_merge && c->x_rem_merge && !early) {
-        a.T2 = ptr<double>(c->dRem); a.ldt2 = dc + 1; a.nb2 = c->x_rem_blocks;
-        a.nb2_dev = reinterpret_cast<const int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1));
-    } else if (!c->in_merge && c->wide_active && c->rem_direct && !early) {
-        a.T2 = rem_rows(c); a.ldt2 = dc + 1; a.nb2 = (c->rem_cap + 15) / 16;
-        a.nb2_dev = rem_count(c);
-    }
-    if (early) { a.P = ptr<double>(c->dPout); a.ldp = d; a.dx0 = ptr<double>(c->dDx); }
+    a.f32_update = (c->cfg.dtype == MSCKF_DTYPE_F32 && !s.two_sources_in_batch) ? 1 : 0;
+    if (s.second) { a.T2 = s.second; a.ldt2 = dc + 1; a.nb2 = s.nb2; a.nb2_dev = s.nb2_dev; }
     a.stamps = nullptr;
-    a.tstamp = c->gs_stamp ? ptr<long long>(c->dGsProg) + 32 : nullptr;
+    a.tstamp = (c->gs_stamp && s.status_word == 0) ? ptr<long long>(c->dGsProg) + 32 : nullptr;
+}
+void launch_k_gain_stream(const GStreamArgs& a, size_t lds, hipStream_t st) {
+    if (a.ns <= GS_WAVES) hipLaunchKernelGGL(k_gain_stream<1>, dim3(a.ns), dim3(64 * GS_WAVES), lds, st, a);
+    else hipLaunchKernelGGL(k_gain_stream<2>, dim3(a.ns), dim3(64 * GS_WAVES), lds, st, a);
 }
 // K6-K7 behind a complete root block: nothing is polled
-int launch_gain_stream(msckf_ctx* c, const double* Tblk, int band) {
+int launch_gain_stream(msckf_ctx* c, const GainSources& s) {
     ++c->gs_epoch;
     GStreamArgs a;
-    fill_gstream_args(c, a, Tblk, band, false);
-    const size_t lds = gstream_lds_doubles(a.ns, a.nb2 > 0 ? a.nb : a.ncb) * 8;
-    if (a.ns <= GS_WAVES) hipLaunchKernelGGL(k_gain_stream<1>, dim3(a.ns), dim3(64 * GS_WAVES), lds, c->stream, a);
-    else hipLaunchKernelGGL(k_gain_stream<2>, dim3(a.ns), dim3(64 * GS_WAVES), lds, c->stream, a);
+    fill_gstream_args(c, a, s, false);
+    launch_k_gain_stream(a, gstream_lds_doubles(a.ns, a.nb2 > 0 ? a.nb : a.ncb) * 8, c->stream);
     HIPCHK(c, hipGetLastError());
-    c->gain_blocked = false;
     return MSCKF_OK;
+}
+// ... the sequential block update where the window takes it (`streamed`: gstream_ok), else round 3's chain of launches
+int launch_gain_behind(msckf_ctx* c, const GainSources& s, bool streamed, RunRecord& rec) {
+    if (streamed) return launch_gain_stream(c, s);
+    rec.word1_ours |= gain_is_blocked(false, c->dc);
+    return launch_gain(c, s.first);
 }
 // K6-K7 on a dense source of rows alone: two row blocks per exchange where the window allows it (k_gdense.h: 7.1 -> 6.1 us per
 // block at N = 30; MSCKF_GAIN_DENSE=0: the one-block kernel)
-void launch_gain_dense_rows(msckf_ctx* c, const GStreamArgs& a, hipStream_t st) {
+int launch_gain_dense_rows(msckf_ctx* c, const GainSources& s, hipStream_t st) {
     static const bool pairs = [] { const char* e = std::getenv("MSCKF_GAIN_DENSE"); return !e || std::atoi(e) != 0; }();
+    ++c->gs_epoch;
+    GStreamArgs a;
+    fill_gstream_args(c, a, s, false);
     const size_t ldsp = gdense_lds_doubles(a.ns, a.nb) * 8;
-    if (pairs && a.nb1 == 0 && a.nb2 > 0 && a.ns <= 14 && ldsp <= (size_t)(LDS_MAX_BYTES - 1024)) {
+    if (pairs && a.nb1 == 0 && a.nb2 > 0 && a.ns <= 14 && ldsp <= (size_t)(LDS_MAX_BYTES - 1024))
         hipLaunchKernelGGL(k_gain_dense, dim3(a.ns), dim3(64 * GS_WAVES), ldsp, st, a);
-        return;
-    }
-    const size_t lds = gstream_lds_doubles(a.ns, a.nb) * 8;
-    if (a.ns <= GS_WAVES) hipLaunchKernelGGL(k_gain_stream<1>, dim3(a.ns), dim3(64 * GS_WAVES), lds, st, a);
-    else hipLaunchKernelGGL(k_gain_stream<2>, dim3(a.ns), dim3(64 * GS_WAVES), lds, st, a);
+    else
+        launch_k_gain_stream(a, gstream_lds_doubles(a.ns, a.nb) * 8, st);
+    HIPCHK(c, hipGetLastError());
+    return MSCKF_OK;
 }
 // MANY dense remainder rows (more than the root sweep's ~110 us cover at ~9 us per block on the nine-wavefront strips of its
 // launch): the update on them runs as a launch of its own, sixteen wavefronts per strip (~7 us per block), on the stream that made
@@ -1771,22 +1790,10 @@ int t2_early_min() {
     static const int m = [] { const char* e = std::getenv("MSCKF_T2_EARLY_MIN"); return e ? std::atoi(e) : 20; }();
     return m;
 }
-int launch_gain_t2_early(msckf_ctx* c, hipStream_t st) {
-    ++c->gs_epoch;
-    GStreamArgs a;
-    const bool keep = c->t2_early;
-    c->t2_early = false;
-    fill_gstream_args(c, a, nullptr, c->dc, false);        // (T2 = the dense rows, no first source)
-    c->t2_early = keep;
-    a.status = ptr<int>(c->dStatus) + 1;
-    a.status_h = nullptr; a.dx_h = nullptr; a.Pout_h = nullptr; a.tstamp = nullptr;
-    if (c->res_direct && c->want_direct) {      // the direct result reads status word 1 from hRes: mirror it there (3: not written)
-        a.status_h = static_cast<int*>(c->hRes) + 1;
-        *a.status_h = 3;
-    }
-    launch_gain_dense_rows(c, a, st);
-    HIPCHK(c, hipGetLastError());
-    return MSCKF_OK;
+// rows: the main update's sources when it takes the dense rows itself
+int launch_gain_t2_early(msckf_ctx* c, GainSources rows, hipStream_t st) {
+    rows.first = nullptr; rows.band = c->dc; rows.status_word = 1;
+    return launch_gain_dense_rows(c, rows, st);
 }
 // K6-K7 on a SECOND source of rows -- the root of the remainder blocks' tree (split long tracks) -- behind the update on the
 // first: the rows of both sources are measurements with independent sigma^2 noise, so the update on all of them is the
@@ -1794,18 +1801,9 @@ int launch_gain_t2_early(msckf_ctx* c, hipStream_t st) {
 // strip after the last exchange, which every workgroup takes part in only after it has loaded its tiles), with the dx row
 // carried on.  Its status goes to word 1.
 int launch_gain_chain(msckf_ctx* c, const double* Tblk) {
-    ++c->gs_epoch;
-    GStreamArgs a;
-    fill_gstream_args(c, a, Tblk, c->dc, false);
-    a.P = ptr<double>(c->dPout); a.ldp = c->d; a.dx0 = ptr<double>(c->dDx);
-    a.T2 = nullptr; a.nb2 = 0; a.nb2_dev = nullptr;
-    a.status = ptr<int>(c->dStatus) + 1;
-    a.status_h = nullptr; a.dx_h = nullptr; a.Pout_h = nullptr; a.tstamp = nullptr;
-    const size_t lds = gstream_lds_doubles(a.ns, a.ncb) * 8;
-    if (a.ns <= GS_WAVES) hipLaunchKernelGGL(k_gain_stream<1>, dim3(a.ns), dim3(64 * GS_WAVES), lds, c->stream, a);
-    else hipLaunchKernelGGL(k_gain_stream<2>, dim3(a.ns), dim3(64 * GS_WAVES), lds, c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    return MSCKF_OK;
+    GainSources s;
+    s.first = Tblk; s.band = c->dc; s.start_from_result = true; s.status_word = 1; s.two_sources_in_batch = true;
+    return launch_gain_stream(c, s);
 }
 // ... on the triangles a cut remainder tree ended with (k_tri_gather laid them down in dRem): a dense second source, nothing else
 int launch_tri_gather(msckf_ctx* c, hipStream_t st) {
@@ -1826,16 +1824,10 @@ int launch_tri_gather(msckf_ctx* c, hipStream_t st) {
     return MSCKF_OK;
 }
 int launch_gain_chain_dense(msckf_ctx* c) {
-    ++c->gs_epoch;
-    GStreamArgs a;
-    fill_gstream_args(c, a, nullptr, c->dc, false);
-    a.P = ptr<double>(c->dPout); a.ldp = c->d; a.dx0 = ptr<double>(c->dDx);
-    a.T2 = ptr<double>(c->dRem); a.ldt2 = c->dc + 1; a.nb2 = (c->rtop_rows + 15) / 16; a.nb2_dev = nullptr;
-    a.status = ptr<int>(c->dStatus) + 1;
-    a.status_h = nullptr; a.dx_h = nullptr; a.Pout_h = nullptr; a.tstamp = nullptr;
-    launch_gain_dense_rows(c, a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return MSCKF_OK;
+    GainSources s;
+    s.band = c->dc; s.second = ptr<double>(c->dRem); s.nb2 = (c->rtop_rows + 15) / 16;
+    s.start_from_result = true; s.status_word = 1; s.two_sources_in_batch = true;
+    return launch_gain_dense_rows(c, s, c->stream);
 }
 // The root sweep (k_sweep form) and K6-K7 in ONE launch (k_root_gain): workgroup 0 sweeps and publishes the rows of the
 // root block as they become final, workgroups 1.. are the strips of the update.  `sa` carries the tables and the node index.
@@ -1847,7 +1839,7 @@ bool root_gain_ok(const msckf_ctx* c, int band) {
 // ([count offsets | tables]) and the root's step-0 requirement count behind its own tables (sweep_gate_table).
 // leaves: the leaves ride too (k_leaf_root_gain), the merge nodes polling them.
 struct MergeRide { int node_base, count, nf, n_gate; const int* flush; size_t lds; };    // lds: what its largest node asks for
-int launch_root_and_gain(msckf_ctx* c, SweepArgs sa, int wtot, int nsteps, const int* flush_tab, const double* Tblk, int band,
+int launch_root_and_gain(msckf_ctx* c, SweepArgs sa, int wtot, int nsteps, const int* flush_tab, const GainSources& gsrc,
                          const MergeRide* ride = nullptr, bool leaves = false) {
     ++c->gs_epoch;
     sa.flush_tab = flush_tab;
@@ -1856,7 +1848,7 @@ int launch_root_and_gain(msckf_ctx* c, SweepArgs sa, int wtot, int nsteps, const
     sa.stamps = nullptr;
     sa.tstamp = c->gs_stamp ? ptr<long long>(c->dGsProg) + 32 : nullptr;      // (behind the progress word, same allocation)
     GStreamArgs ga;
-    fill_gstream_args(c, ga, Tblk, band, true);
+    fill_gstream_args(c, ga, gsrc, true);
     // (every workgroup asks for more than half of a CU's LDS: one per CU, the sweep has its CU to itself)
     size_t lds = std::max<size_t>(std::max(sweep_lds_bytes_fl(wtot, SWEEP_NW, nsteps), gstream_lds_doubles(ga.ns, ga.nb2 > 0 ? ga.nb : ga.ncb) * 8),
                                   (size_t)84 * 1024);
@@ -1885,14 +1877,12 @@ int launch_root_and_gain(msckf_ctx* c, SweepArgs sa, int wtot, int nsteps, const
         hipLaunchKernelGGL((k_leaf_root_gain<SWEEP_NW, 2>), dim3(c->n_leaves + nm + 1 + ga.ns), dim3(64 * (SWEEP_NW + 1)), lds, c->stream,
                            la, ma, sa, ga, c->n_leaves, nm);
         HIPCHK(c, hipGetLastError());
-        c->gain_blocked = false;
         return MSCKF_OK;
     }
     if (leaves) { c->last_error = "k_leaf_root_gain: the plan has no merge level for the leaves"; return MSCKF_ERR_STATE; }
     if (mid) hipLaunchKernelGGL((k_root_gain_m<SWEEP_NW, SWEEP_NW_MID, 2>), dim3(1 + ga.ns + nm), dim3(64 * (SWEEP_NW_MID + 1)), lds, c->stream, sa, ga, ma);
     else hipLaunchKernelGGL((k_root_gain<SWEEP_NW, 2>), dim3(1 + ga.ns + nm), dim3(64 * (SWEEP_NW + 1)), lds, c->stream, sa, ga, ma);
     HIPCHK(c, hipGetLastError());
-    c->gain_blocked = false;
     return MSCKF_OK;
 }
 
@@ -1902,7 +1892,7 @@ bool root_gain_w_ok(const msckf_ctx* c, int band) {
            2 * (2 + (c->dc + 15) / 16) <= c->n_cu;                                             // (as root_gain_ok: the sweep and the strips wait for each other)
 }
 template <int CS>
-int launch_root_and_gain_w(msckf_ctx* c, int node, int nsteps, int rc_log2, const double* zero, const double* Tblk, int band) {
+int launch_root_and_gain_w(msckf_ctx* c, int node, int nsteps, int rc_log2, const double* zero, const GainSources& gsrc) {
     ++c->gs_epoch;
     WSweepArgs a{};
     a.nodes = ptr<SweepNode>(c->dSweepNodes);
@@ -1917,7 +1907,7 @@ int launch_root_and_gain_w(msckf_ctx* c, int node, int nsteps, int rc_log2, cons
     a.epoch = c->gs_epoch;
     a.tstamp = c->gs_stamp ? ptr<long long>(c->dGsProg) + 32 : nullptr;
     GStreamArgs ga;
-    fill_gstream_args(c, ga, Tblk, band, true);
+    fill_gstream_args(c, ga, gsrc, true);
     const size_t lds = std::max<size_t>(std::max(wsweep_lds_bytes<CS>(1 << rc_log2, SWEEP_NW, nsteps),
                                                  gstream_lds_doubles(ga.ns, ga.nb2 > 0 ? ga.nb : ga.ncb) * 8), (size_t)84 * 1024);
     if (ga.ns <= 2 * (SWEEP_NW - 1))
@@ -1925,7 +1915,6 @@ int launch_root_and_gain_w(msckf_ctx* c, int node, int nsteps, int rc_log2, cons
     else
         hipLaunchKernelGGL((k_root_gain_w<SWEEP_NW, CS, 3>), dim3(1 + ga.ns), dim3(64 * SWEEP_NW), lds, c->stream, a, ga);
     HIPCHK(c, hipGetLastError());
-    c->gain_blocked = false;
     return MSCKF_OK;
 }
 
@@ -1952,9 +1941,46 @@ int gate_counts(msckf_ctx* c, int out[4], std::vector<unsigned char>* acc_sorted
 
 const double* root_block(msckf_ctx* c) { return ptr<double>(c->dRbuf) + c->root_off; }
 
+// Every launch of the run is in the stream: its record becomes the one the readers decide from.
+void finish_run(msckf_ctx* c, RunRecord rec) {
+    rec.ran = true;
+    rec.serial = c->last.serial + 1;
+    c->last = rec;
+    c->run_pending = true;
+}
+
+// The last run's outcome from the head of the result range and the gate's accepted count; n_acc: the count that decided it.
+Outcome run_outcome(const RunRecord& r, const int status[5], int gate_accepted, int* n_acc) {
+    *n_acc = r.acc == AccSource::Word2 ? status[2] : r.acc == AccSource::Fixed ? r.accepted : gate_accepted;
+    return decode_outcome(r.gain, r.word1_ours, r.word4_ours, *n_acc, status);
+}
+// ... as the C ABI reports it
+int outcome_rc(msckf_ctx* c, Outcome o) {
+    switch (o) {
+        case Outcome::Ok: return MSCKF_OK;
+        case Outcome::Noop: return MSCKF_NOOP;
+        case Outcome::NotSpd: return MSCKF_ERR_NOT_SPD;     // a non-positive pivot leaves garbage in P_out: the prior is kept
+        case Outcome::Timeout: c->last_error = "k_gain_stream: timeout (the root sweep or a workgroup of the update did not make progress)"; return MSCKF_ERR_HIP;
+        case Outcome::Unwritten: c->last_error = "K6-K7 did not report a status"; return MSCKF_ERR_HIP;
+        case Outcome::Overflow: c->last_error = "split records: more remainder rows than the merge takes"; return MSCKF_ERR_STATE;
+    }
+    return MSCKF_ERR_STATE;
+}
+// MSCKF_DEBUG_FAKE_TIMEOUT=1 (tests), once per context: the first streamed update of a context reads as timed out (msckf_get_result;
+// fused with the root sweep up to 53 clones, a k_gain_stream launch of its own at 54 - 82, whose workgroups wait for each other all
+// the same), or the first early update of a merge does (run_merge_groups sets its status word)
+bool take_fake_timeout(msckf_ctx* c) {
+    static const bool fake = [] { const char* e = std::getenv("MSCKF_DEBUG_FAKE_TIMEOUT"); return e && std::atoi(e) == 1; }();
+    if (!fake || c->fake_timeout_done) return false;
+    c->fake_timeout_done = true;
+    return true;
+}
+
 int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     if (!c->have_state || !c->have_features) return MSCKF_ERR_STATE;
     int rc;
+    RunRecord rec;
+    rec.kind = RunKind::Pipeline; rec.gain = with_gain;
     if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[0], c->stream));
     if (c->state_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_state, 0)); c->state_pending = false; }
     if (!c->feature_launched && (rc = launch_feature(c)) != MSCKF_OK) return rc;
@@ -1978,7 +2004,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     // the leaves inside the root's launch (k_leaf_root_gain): a plan made for it (no split long tracks) whose root runs beside K6-K7
     const bool fuse_leaves = c->F > 0 && c->band_plan && c->leaf_fused && with_gain && c->root >= 0 && c->sweep_mode == 0 &&
                              gstream_ok(c, c->root_band) && !c->h_root_flush.empty() && root_gain_ok(c, c->root_band);
-    c->leaves_fused_last = fuse_leaves;
+    rec.fused_leaves = fuse_leaves;
     if (c->F > 0 && c->band_plan && !fuse_leaves && (rc = launch_leaves_band(c, early ? c->n_leaves0 : 0)) != MSCKF_OK) return rc;
     if (c->F > 0 && !c->band_plan && (rc = launch_fold_levels(c, c->levels, c->nodes)) != MSCKF_OK) return rc;
     // (a rank that exports its group triangles stops in front of the root sweep: rank 0 runs it over all shards)
@@ -1989,20 +2015,27 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     // (split long tracks' second source of rows -- a tree's root or triangles, or the dense rows -- needs the streamed K6-K7)
     if ((chain || direct) && with_gain && !gs) { c->last_error = "split long tracks need the streamed K6-K7"; return MSCKF_ERR_STATE; }
     // (known before the early launch below: that launch mirrors its status word into hRes when this run's result is direct)
-    c->res_direct = c->want_direct && c->gate_direct && gs && !chain;       // (a second update behind the first writes the HBM copies only)
-    {
-        c->t2_early = direct && with_gain && c->root >= 0 && gstream_ok(c, c->root_band) && (c->rem_cap + 15) / 16 >= t2_early_min();
-        if (c->t2_early) {
-            hipStream_t rs = c->wide_on_stream2 ? c->stream2 : c->stream;
-            if ((rc = launch_gain_t2_early(c, rs)) != MSCKF_OK) return rc;
-            if (c->wide_on_stream2) HIPCHK(c, hipEventRecord(c->ev_rem, c->stream2));
-        }
+    rec.direct = c->want_direct && c->gate_direct && gs && !chain;       // (a second update behind the first writes the HBM copies only)
+    // the run's main update: on the root block and, unless a launch of their own takes them first, the dense remainder rows
+    GainSources src;
+    src.first = c->root >= 0 ? root_block(c) : nullptr; src.band = c->root_band;
+    src.mirror = rec.direct ? c->hRes : nullptr;
+    src.two_sources_in_batch = c->wide_active;
+    if (direct) { src.second = rem_rows(c); src.nb2 = (c->rem_cap + 15) / 16; src.nb2_dev = rem_count(c); }
+    // the dense remainder rows are applied by a launch of their own; the update on the band root starts from its P_out / dx
+    const bool t2_early = direct && with_gain && c->root >= 0 && gstream_ok(c, c->root_band) && (c->rem_cap + 15) / 16 >= t2_early_min();
+    if (t2_early) {
+        hipStream_t rs = c->wide_on_stream2 ? c->stream2 : c->stream;
+        if ((rc = launch_gain_t2_early(c, src, rs)) != MSCKF_OK) return rc;
+        if (c->wide_on_stream2) HIPCHK(c, hipEventRecord(c->ev_rem, c->stream2));
+        src.second = nullptr; src.nb2 = 0; src.nb2_dev = nullptr;
+        src.start_from_result = true;
     }
     // (behind an early update on the dense remainder rows the root sweep runs as a launch of its own, BESIDE that update, and the update
     //  on its rows follows both: in one launch with it the sweep would wait for the remainder rows' update too -- a frame of 300 tracks
     //  ~ U[2, 30]: 695 -> ~610 us)
     static const bool t2_split = [] { const char* e = std::getenv("MSCKF_T2_SPLIT_ROOT"); return !e || std::atoi(e) != 0; }();
-    const bool beside = gs && c->band_plan && c->root >= 0 && !(c->t2_early && t2_split) &&
+    const bool beside = gs && c->band_plan && c->root >= 0 && !(t2_early && t2_split) &&
                         (c->sweep_mode == 0 ? (!c->h_root_flush.empty() && root_gain_ok(c, c->root_band)) : root_gain_w_ok(c, c->root_band));
     const bool streamed = beside && c->sweep_mode == 0 && c->root_streamed;     // the last merge level rides in the root's launch
     if (fuse_leaves && !streamed) { c->last_error = "k_leaf_root_gain: the root does not run beside K6-K7"; return MSCKF_ERR_STATE; }
@@ -2014,14 +2047,14 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
                            c->xmask_doubles > 0 ? reinterpret_cast<unsigned char*>(ptr<double>(c->dRbuf) + c->N + 1) : nullptr);
         HIPCHK(c, hipGetLastError());
     }
-    if (c->t2_early && c->wide_on_stream2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));     // (its P_out / dx are what the update below starts from)
-    c->gs_fused_last = beside;
-    c->gs_last = gs;
+    if (t2_early && c->wide_on_stream2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));     // (its P_out / dx are what the update below starts from)
+    rec.fused_root = beside;
+    rec.streamed_gain = gs;
     if (beside && c->sweep_mode > 0) {
         const SweepNode& rn = c->snodes.back();
         const double* zero = ptr<double>(c->dRbuf) + c->zero_off;
-        if (c->sweep_mode == 1) rc = launch_root_and_gain_w<4>(c, c->n_group_merges, rn.nsteps, WS_RC_LOG2_4, zero, root_block(c), c->root_band);
-        else rc = launch_root_and_gain_w<6>(c, c->n_group_merges, rn.nsteps, WS_RC_LOG2_6, zero, root_block(c), c->root_band);
+        if (c->sweep_mode == 1) rc = launch_root_and_gain_w<4>(c, c->n_group_merges, rn.nsteps, WS_RC_LOG2_4, zero, src);
+        else rc = launch_root_and_gain_w<6>(c, c->n_group_merges, rn.nsteps, WS_RC_LOG2_6, zero, src);
         if (rc != MSCKF_OK) return rc;
         if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[2], c->stream));
     } else if (beside) {
@@ -2040,30 +2073,21 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
             for (int i = lv.first; i < lv.first + lv.second; ++i)
                 ride.lds = std::max(ride.lds, sweep_lds_bytes_fl(c->snodes[i].wtot, ride.nf, c->snodes[i].nsteps, fuse_leaves ? c->snodes[i].n_gate : -1));
         }
-        if ((rc = launch_root_and_gain(c, a, c->snodes.back().wtot, c->snodes.back().nsteps, ptr<int>(c->dRootFlush), root_block(c),
-                                       c->root_band, streamed ? &ride : nullptr, fuse_leaves)) != MSCKF_OK) return rc;
+        if ((rc = launch_root_and_gain(c, a, c->snodes.back().wtot, c->snodes.back().nsteps, ptr<int>(c->dRootFlush), src,
+                                       streamed ? &ride : nullptr, fuse_leaves)) != MSCKF_OK) return rc;
         if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[2], c->stream));
     } else {
         if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[2], c->stream));
-        if (with_gain && c->F > 0 && have_rows) {
-            if (gs) rc = launch_gain_stream(c, c->root >= 0 ? root_block(c) : nullptr, c->root_band);
-            else rc = launch_gain(c, root_block(c));
-            if (rc != MSCKF_OK) return rc;
-        }
+        if (with_gain && c->F > 0 && have_rows && (rc = launch_gain_behind(c, src, gs, rec)) != MSCKF_OK) return rc;
     }
     if (chain && with_gain) {              // the remainder blocks' rows: a second update behind the first
         if (c->wide_on_stream2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));
         if ((rc = c->rtops.empty() ? launch_gain_chain(c, ptr<double>(c->dRbuf) + c->rroot_off) : launch_gain_chain_dense(c)) != MSCKF_OK) return rc;
     }
     if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[3], c->stream));
-    c->ran = true;
-    c->ran_gain = with_gain;
-    c->acc_override = -1;
-    c->acc_from_dev = false;
     // status word 1 is this run's only where a launch of this run wrote it; otherwise it is stale (nothing resets it between runs)
-    c->x_status1 = with_gain && (chain || c->t2_early); c->x_rem_last = false;
-    ++c->run_serial; c->run_pending = true;
-    if (c->res_direct) c->direct_serial = c->run_serial;
+    rec.word1_ours |= with_gain && (chain || t2_early);
+    finish_run(c, rec);
     return MSCKF_OK;
 }
 
@@ -2472,7 +2496,7 @@ int msckf_set_state(msckf_ctx* c, int32_t N, const double* P, const double* cam_
     else { HIPCHK(c, hipEventRecord(c->ev_state, c->stream_up)); c->state_pending = true; }
     c->us_h2d = (float)(now_us() - t0);
     c->have_state = true;
-    c->ran = false;
+    c->last.ran = false;
     tracks_clear(c);                      // clone slots lose their meaning
     return MSCKF_OK;
 }
@@ -2493,7 +2517,7 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     // standing over arenas / plan that describe another F (run() then returns MSCKF_ERR_STATE)
     c->have_features = false;
     c->feature_launched = false;
-    c->ran = false;
+    c->last.ran = false;
     c->have_tracks = false;
     c->use_select = false;
     c->batch_from_store = false;
@@ -2966,7 +2990,7 @@ int msckf_run_timed(msckf_ctx* c, int32_t iters, float* ms_total, float* stage_u
                 HIPCHK(c, hipEventElapsedTime(&t, c->ev[s], c->ev[s + 1]));
                 acc[s] += t * 1000.0;
             }
-            if (c->gs_fused_last) {
+            if (c->last.fused_root) {
                 // one launch holds the root sweep and K6-K7: what trails the sweep's last published row is K6-K7's share
                 long long ts[3] = {0, 0, 0};
                 HIPCHK(c, hipMemcpy(ts, ptr<long long>(c->dGsProg) + 32, 24, hipMemcpyDeviceToHost));
@@ -2978,7 +3002,7 @@ int msckf_run_timed(msckf_ctx* c, int32_t iters, float* ms_total, float* stage_u
                     for (int b = 0; b < (c->dc + 15) / 16 && b < 15; ++b) std::fprintf(stderr, " %.1f", (t8[3 + b] - t8[0]) * 0.01);
                     std::fprintf(stderr, " | the flusher published them at");
                     for (int b = 1; b < (c->dc + 15) / 16 && b < 14; ++b) std::fprintf(stderr, " %.1f", (t8[18 + b] - t8[0]) * 0.01);
-                    if (c->leaves_fused_last)
+                    if (c->last.fused_leaves)
                         std::fprintf(stderr, " | launch head -> root's first step %.1f us, -> last row %.1f, -> update done %.1f",
                                      (t8[33] - t8[32]) * 0.01, (t8[1] - t8[32]) * 0.01, (t8[2] - t8[32]) * 0.01);
                     std::fprintf(stderr, "\n");
@@ -2994,14 +3018,14 @@ int msckf_run_timed(msckf_ctx* c, int32_t iters, float* ms_total, float* stage_u
 
 int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted, msckf_stats* st) {
     if (!c) return MSCKF_ERR_ARG;
-    if (!c->ran) return MSCKF_ERR_STATE;
+    if (!c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const double t0 = now_us();
     const size_t d = c->d;
+    const RunRecord& r = c->last;
     // gate results and (when the gain stage ran) status | dx | P_out: two copies behind the pipeline, one sync
     if (c->F > 0 && !c->gate_direct) HIPCHK(c, hipMemcpyAsync(c->hGate, c->dGateArena.p, (size_t)c->Fs * 5, hipMemcpyDeviceToHost, c->stream));
-    const bool direct = c->res_direct && c->direct_serial == c->run_serial;     // (a merge behind the update wrote the HBM arena only)
-    if (c->ran_gain && !direct) {
+    if (r.gain && !r.direct) {
         const size_t bytes = P_out ? c->res_p_off + d * d * 8 : c->res_dx_off + d * 8;
         HIPCHK(c, hipMemcpyAsync(c->hRes, c->dResArena.p, bytes, hipMemcpyDeviceToHost, c->stream));
     }
@@ -3011,32 +3035,20 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
     int counters[4] = {0, 0, 0, 0};
     int status[5] = {0};
     std::vector<unsigned char> acc_sorted;
-    const bool gate_done = c->gate_serial == c->run_serial && (!accepted || accepted == c->gate_mask_dst);
+    const bool gate_done = c->gate_serial == r.serial && (!accepted || accepted == c->gate_mask_dst);
     if (gate_done) std::memcpy(counters, c->gate_cnt, sizeof(counters));
     else if (int rc0 = gate_counts(c, counters, &acc_sorted, true)) return rc0;
-    if (c->ran_gain) std::memcpy(status, c->hRes, 20);
-    if (!c->x_rem_last) status[4] = 0;
-    const int n_acc = c->acc_from_dev ? status[2] : (c->acc_override >= 0) ? c->acc_override : counters[0];
-    if (!(c->ran_gain && n_acc > 0)) status[0] = status[1] = 0;
-    int rc = (n_acc == 0) ? MSCKF_NOOP : MSCKF_OK;
-    if (rc == MSCKF_OK && c->ran_gain && (status[0] != 0 || ((c->gain_blocked || c->x_status1) && status[1] != 0))) rc = MSCKF_ERR_NOT_SPD;
-    if (rc == MSCKF_OK && (status[4] & 2)) { c->last_error = "split records: more remainder rows than the merge takes"; rc = MSCKF_ERR_STATE; }
-    if (rc == MSCKF_ERR_NOT_SPD && (status[0] == 3 || (c->x_status1 && status[1] == 3))) {   // a mirror of a status word in host memory was never written
-        c->last_error = "K6-K7 did not report a status";
-        rc = MSCKF_ERR_HIP;
-    }
-    {   // MSCKF_DEBUG_FAKE_TIMEOUT=1 (tests): the first streamed update of a context reads as timed out (fused with the root sweep
-        // up to 53 clones; a k_gain_stream launch of its own at 54 - 82, whose workgroups wait for each other all the same)
-        static const bool fake = [] { const char* e = std::getenv("MSCKF_DEBUG_FAKE_TIMEOUT"); return e && std::atoi(e) == 1; }();
-        if (fake && !c->fake_timeout_done && rc == MSCKF_OK && c->ran_gain && c->gs_last) { c->fake_timeout_done = true; status[0] = 2; rc = MSCKF_ERR_NOT_SPD; }
-    }
-    if (rc == MSCKF_ERR_NOT_SPD && (status[0] == 2 || (c->x_status1 && status[1] == 2))) {       // k_gain_stream gave up waiting for rows of T or for another workgroup
+    if (r.gain) std::memcpy(status, c->hRes, 20);
+    int n_acc;
+    Outcome o = run_outcome(r, status, counters[0], &n_acc);
+    if (o == Outcome::Ok && r.gain && r.streamed_gain && take_fake_timeout(c)) o = Outcome::Timeout;
+    if (o == Outcome::Timeout) {          // k_gain_stream gave up waiting for rows of T or for another workgroup
         // The workgroups of k_root_gain / k_gain_stream wait for each other inside their launch; that they are all resident is
         // argued from their LDS footprint and the device's CU count, not promised by HIP: a partitioned or busy
         // device can keep one out until the 0.5 s bound.  ONE retry on kernels that never wait inside a launch (separate merge
         // levels and root, round 3's K6-K7 launches), and the context stays on them.  Not with split long tracks in the batch
-        // (their second source of rows needs the sequential block update).
-        if (c->have_features && !c->split_on && !c->x_status1 && !c->retry_plain && c->gs_enabled) {
+        // (their second source of rows needs the sequential block update), and not a merge (its rows are not this context's batch).
+        if (r.kind == RunKind::Pipeline && c->have_features && !c->split_on && !r.word1_ours && !c->retry_plain && c->gs_enabled) {
             c->retry_plain = true;
             c->gs_enabled = false; c->stream_enabled = false;
             if (int r2 = replan_current(c, false)) return r2;
@@ -3045,25 +3057,24 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
             c->last_error = "k_gain_stream timed out once: this context now runs its sweeps and K6-K7 as separate launches";
             return r3;
         }
-        c->last_error = "k_gain_stream: timeout (the root sweep or a workgroup of the update did not make progress)";
-        rc = MSCKF_ERR_HIP;
     }
+    const int rc = outcome_rc(c, o);
     if (accepted && c->F > 0 && !gate_done) {
         for (int s = 0; s < c->F; ++s) accepted[c->perm[s]] = (acc_sorted[s] == 1) ? 1 : 0;
     }
     const char* hres = static_cast<const char*>(c->hRes);
     if (dx) {
-        if (rc == MSCKF_OK && c->ran_gain) std::memcpy(dx, hres + c->res_dx_off, d * 8);
+        if (rc == MSCKF_OK && r.gain) std::memcpy(dx, hres + c->res_dx_off, d * 8);
         else std::memset(dx, 0, d * 8);
     }
     if (P_out) {
         // no-op leaves the covariance untouched (reference early returns MSCKF.py:584-585)
-        if (rc == MSCKF_OK && c->ran_gain) { if (c->pool) c->pool->copy(P_out, hres + c->res_p_off, d * d * 8); else std::memcpy(P_out, hres + c->res_p_off, d * d * 8); }
+        if (rc == MSCKF_OK && r.gain) { if (c->pool) c->pool->copy(P_out, hres + c->res_p_off, d * d * 8); else std::memcpy(P_out, hres + c->res_p_off, d * d * 8); }
         else HIPCHK(c, hipMemcpy(P_out, c->dP.p, d * d * 8, hipMemcpyDeviceToHost));
     }
     c->us_d2h = (float)(now_us() - t0);
     c->hp[8] += tsync - t0; c->hp[9] += now_us() - tsync;
-    c->fetched_serial = c->run_serial; c->fetched_rc = rc;
+    c->fetched_serial = r.serial; c->fetched_rc = rc;
     if (st) {
         std::memset(st, 0, sizeof(*st));
         st->n_features = c->F - counters[3]; st->n_accepted = n_acc;
@@ -3073,8 +3084,8 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
         st->stacked_rows = counters[1]; st->not_spd = counters[2];
         st->n_leaves = c->n_leaves;
         st->n_levels = (int)c->levels.size() + (c->band_plan ? (int)c->sweep_levels.size() + 1 : 0);
-        st->k5_launches = st->n_levels - ((c->band_plan && c->gs_fused_last && c->sweep_mode == 0 && c->root_streamed) ? 1 : 0)   // (a streamed merge level rides in the root's launch)
-                          - ((c->band_plan && c->gs_fused_last && c->leaves_fused_last) ? 1 : 0);                                  // (... and the leaves with it)
+        st->k5_launches = st->n_levels - ((c->band_plan && r.fused_root && c->sweep_mode == 0 && c->root_streamed) ? 1 : 0)   // (a streamed merge level rides in the root's launch)
+                          - ((c->band_plan && r.fused_root && r.fused_leaves) ? 1 : 0);                                  // (... and the leaves with it)
         st->us_total = c->us_total; st->us_feature = c->us_stage[0]; st->us_qr = c->us_stage[1];
         st->us_gain = c->us_stage[2];
         st->us_host_prep = c->us_host_prep; st->us_h2d = c->us_h2d; st->us_d2h = c->us_d2h;
@@ -3083,9 +3094,9 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
 }
 
 int msckf_commit_covariance(msckf_ctx* c) {
-    if (!c || !c->ran || !c->ran_gain) return MSCKF_ERR_STATE;
+    if (!c || !c->last.ran || !c->last.gain) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->fetched_serial == c->run_serial) {          // msckf_get_result has already decided this run: no second read-back
+    if (c->fetched_serial == c->last.serial) {          // msckf_get_result has already decided this run: no second read-back
         if (c->fetched_rc != MSCKF_OK) return c->fetched_rc;
         HIPCHK(c, hipMemcpyAsync(c->dP.p, c->dPout.p, (size_t)c->d * c->d * 8, hipMemcpyDeviceToDevice, c->stream));
         c->main_busy = true;                           // (stays in the stream: every reader of P is behind it)
@@ -3093,14 +3104,10 @@ int msckf_commit_covariance(msckf_ctx* c) {
     }
     int counters[4] = {0, 0, 0, 0};
     if (int rc0 = gate_counts(c, counters, nullptr)) return rc0;
-    // a non-positive Cholesky pivot leaves garbage in P_out: keep the prior (msckf_get_result reports the same code)
-    int status[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(status, c->dStatus.p, 16, hipMemcpyDeviceToHost, c->stream));
+    int status[5] = {0, 0, 0, 0, 0}, n_acc;
+    HIPCHK(c, hipMemcpyAsync(status, c->dStatus.p, 20, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int n_acc = c->acc_from_dev ? status[2] : (c->acc_override >= 0) ? c->acc_override : counters[0];
-    if (n_acc == 0) return MSCKF_NOOP;
-    if (status[0] == 2 || (c->x_status1 && status[1] == 2)) return MSCKF_ERR_HIP;   // k_gain_stream timed out
-    if (status[0] != 0 || ((c->gain_blocked || c->x_status1) && status[1] != 0)) return MSCKF_ERR_NOT_SPD;
+    if (int rc = outcome_rc(c, run_outcome(c->last, status, counters[0], &n_acc))) return rc;      // (msckf_get_result reports the same code)
     HIPCHK(c, hipMemcpyAsync(c->dP.p, c->dPout.p, (size_t)c->d * c->d * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MSCKF_OK;
@@ -3113,7 +3120,7 @@ int msckf_update(msckf_ctx* c, int32_t N, const double* P, const double* cam_R, 
                  int32_t n_crit, double* dx, double* P_out, uint8_t* accepted, msckf_stats* stats) {
     if (!c) return MSCKF_ERR_ARG;
     const double tu0 = now_us();
-    if (c->main_busy || (c->ran && c->fetched_serial != c->run_serial)) {       // work nobody waited for: the side stream below must not overtake it
+    if (c->main_busy || (c->last.ran && c->fetched_serial != c->last.serial)) {       // work nobody waited for: the side stream below must not overtake it
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->main_busy = c->feat_busy = c->pose_busy = c->run_pending = false;
     }
@@ -3164,7 +3171,7 @@ int msckf_update(msckf_ctx* c, int32_t N, const double* P, const double* cam_R, 
             if (accepted) accepted[perm[s]] = a == 1 ? 1 : 0;
         }
         std::memcpy(c->gate_cnt, cnt, sizeof(cnt));
-        c->gate_serial = c->run_serial; c->gate_mask_dst = accepted;
+        c->gate_serial = c->last.serial; c->gate_mask_dst = accepted;
         c->gate_event = false;
         c->hp[11] += now_us() - tg0;
     }
@@ -3234,7 +3241,7 @@ int msckf_run_select(msckf_ctx* c, const msckf_select_params* sp) {
     if (sp->width < 1 || sp->height < 1) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     c->use_select = true;
-    c->ran = false;
+    c->last.ran = false;
     c->sel_params = *sp;
     if (c->F == 0) return MSCKF_OK;
     SelectArgs a{};
@@ -3285,7 +3292,7 @@ int msckf_replan(msckf_ctx* c) {
     if (int rcp = upload_plan(c)) return rcp;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->us_host_prep = (float)(now_us() - t0);
-    c->ran = false;
+    c->last.ran = false;
     return MSCKF_OK;
 }
 
@@ -3294,7 +3301,7 @@ int msckf_debug_time_select(msckf_ctx* c, int32_t iters, float* us_per_launch) {
     if (!c->use_select) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const msckf_select_params sp = c->sel_params;
-    const bool ran = c->ran;
+    const bool ran = c->last.ran;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
     for (int i = 0; i < iters; ++i)
@@ -3304,14 +3311,14 @@ int msckf_debug_time_select(msckf_ctx* c, int32_t iters, float* us_per_launch) {
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev[4], c->ev[5]));
     *us_per_launch = ms * 1000.0f / iters;
-    c->ran = ran;                                                // outputs unchanged: results stay valid
+    c->last.ran = ran;                                                // outputs unchanged: results stay valid
     return MSCKF_OK;
 }
 
 int msckf_clear_selection(msckf_ctx* c) {
     if (!c) return MSCKF_ERR_ARG;
     c->use_select = false;
-    c->ran = false;
+    c->last.ran = false;
     return MSCKF_OK;
 }
 
@@ -3402,7 +3409,7 @@ int msckf_propagate(msckf_ctx* c, const double* Phi, const double* Q) {
         hipLaunchKernelGGL(k_symmetrize_tail, dim3(nb, nb), dim3(256), 0, c->stream, ptr<double>(c->dP), c->d, 15);
     }
     HIPCHK(c, hipGetLastError());
-    c->ran = false;                       // results of a previous update refer to the old prior
+    c->last.ran = false;                       // results of a previous update refer to the old prior
     return MSCKF_OK;
 }
 
@@ -3488,7 +3495,7 @@ int msckf_set_poses(msckf_ctx* c, const double* cam_R, const double* cam_t, cons
     c->h_cam[2].assign(cam_R0, cam_R0 + N * 9); c->h_cam[3].assign(cam_t0, cam_t0 + N * 3);
     if (int rc = upload_poses(c)) return rc;       // (stays in the stream: whatever reads the poses is behind it)
     c->main_busy = true;
-    c->ran = false;
+    c->last.ran = false;
     return MSCKF_OK;
 }
 
@@ -3562,7 +3569,7 @@ int msckf_propagate_imu(msckf_ctx* c, int32_t n, const double* gyro, const doubl
     }
     HIPCHK(c, hipGetLastError());
     c->main_busy = true;
-    c->ran = false;                       // results of a previous update refer to the old prior
+    c->last.ran = false;                       // results of a previous update refer to the old prior
     return MSCKF_OK;
 }
 
@@ -3751,7 +3758,7 @@ size_t msckf_block_doubles(const msckf_ctx* c) { return c ? (size_t)c->dc * (c->
 
 int msckf_export_block(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accepted) {
     if (!c || !dst) return MSCKF_ERR_ARG;
-    if (!c->ran) return MSCKF_ERR_STATE;
+    if (!c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = msckf_block_doubles(c) * 8;
     if (c->F == 0 || c->root < 0) {
@@ -3761,7 +3768,7 @@ int msckf_export_block(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accep
         if (n_accepted) *n_accepted = 0;
         return MSCKF_OK;
     }
-    if (c->xchg_planned && !c->ran_gain) return MSCKF_ERR_STATE;   // the root sweep was left to the merging rank: msckf_export_groups
+    if (c->xchg_planned && !c->last.gain) return MSCKF_ERR_STATE;   // the root sweep was left to the merging rank: msckf_export_groups
     HIPCHK(c, hipMemcpyAsync(dst, root_block(c), bytes, device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                              c->stream));
     int counters[4] = {0, 0, 0, 0};
@@ -3770,25 +3777,41 @@ int msckf_export_block(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accep
     return MSCKF_OK;
 }
 
-// (x_rem_merge describes the merge being launched only: a later merge of another kind must not inherit it)
-struct MergeScope {
-    msckf_ctx* c;
-    explicit MergeScope(msckf_ctx* c_) : c(c_) { c->in_merge = true; c->x_rem_merge = false; }
-    ~MergeScope() { c->in_merge = false; c->x_rem_merge = false; }
-};
+namespace {
+// The merges work behind the local plan's region of the workspace: grow it to `need` bytes, keeping the local plan's blocks
+int grow_workspace(msckf_ctx* c, size_t need) {
+    if (c->dRbuf.bytes >= need) return MSCKF_OK;
+    void* np = nullptr;
+    HIPCHK(c, hipMalloc(&np, need));
+    HIPCHK(c, hipMemset(np, 0, need));
+    if (c->dRbuf.p) {
+        HIPCHK(c, hipMemcpy(np, c->dRbuf.p, std::min(c->dRbuf.bytes, c->gather_off * 8), hipMemcpyDeviceToDevice));
+        HIPCHK(c, hipFree(c->dRbuf.p));
+    }
+    c->dRbuf.p = np; c->dRbuf.bytes = need;
+    c->x_plan_valid = false;              // (a cached merge plan names offsets from the old base)
+    return MSCKF_OK;
+}
+// A merge has its own sources of rows, whatever the rank's own last batch looked like, and status words 1 and 4 are its own: nothing
+// an earlier batch or merge left there may be read as its outcome
+int begin_merge(msckf_ctx* c) {
+    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 1, 0, 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 4, 0, 4, c->stream));
+    return MSCKF_OK;
+}
+}  // namespace
 
 int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int device_ptr,
                          int32_t total_accepted) {
     if (!c || !blocks || n_blocks < 1) return MSCKF_ERR_ARG;
-    MergeScope merge_scope(c);
     if (!c->have_state) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
-    const int N = c->N, dc = c->dc;
+    const int dc = c->dc;
     const size_t blk = (size_t)dc * (dc + 1);
-    // ONE source of rows; status words 1 and 4 are this merge's (an earlier merge of split records wrote them)
-    c->t2_early = false; c->x_status1 = false; c->x_rem_last = false;
-    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 1, 0, 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 4, 0, 4, c->stream));
+    RunRecord rec;
+    rec.kind = RunKind::RootMerge; rec.gain = true;
+    if (total_accepted >= 0) { rec.acc = AccSource::Fixed; rec.accepted = total_accepted; }     // (decides OK / NOOP in msckf_get_result)
+    if (int rc = begin_merge(c)) return rc;
     // workspace: gathered blocks + merge outputs, behind the local plan's region
     std::vector<FoldNode> nodes;
     std::vector<std::pair<int, int>> levels;
@@ -3810,18 +3833,7 @@ int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int
         base = nb; cnt = (int)nodes.size() - nb;
         levels.push_back({base, cnt});
     }
-    const size_t need = (off + 16) * 8;
-    if (c->dRbuf.bytes < need) {
-        // grow, keeping the local plan's blocks
-        void* np = nullptr;
-        HIPCHK(c, hipMalloc(&np, need));
-        HIPCHK(c, hipMemset(np, 0, need));
-        if (c->dRbuf.p) {
-            HIPCHK(c, hipMemcpy(np, c->dRbuf.p, std::min(c->dRbuf.bytes, c->gather_off * 8), hipMemcpyDeviceToDevice));
-            HIPCHK(c, hipFree(c->dRbuf.p));
-        }
-        c->dRbuf.p = np; c->dRbuf.bytes = need;
-    }
+    if (int rc = grow_workspace(c, (off + 16) * 8)) return rc;
     double* rb = ptr<double>(c->dRbuf);
     HIPCHK(c, hipMemsetAsync(rb + c->gather_off, 0, (off - c->gather_off) * 8, c->stream));
     HIPCHK(c, hipMemcpyAsync(rb + c->gather_off, blocks, (size_t)n_blocks * blk * 8,
@@ -3835,18 +3847,12 @@ int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int
     HIPCHK(c, hipMemcpyAsync(c->dNodes.p, all.data(), all.size() * sizeof(FoldNode), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!levels.empty()) { if (int rc = launch_fold_levels(c, levels, all)) return rc; }
-    const double* root = rb + all.back().out_off;
-    // counters[0] decides OK / NOOP in get_result: mark "accepted" when any block is non-empty
-    (void)N;
-    int rc;
-    if (gstream_ok(c, dc)) rc = launch_gain_stream(c, root, dc);
-    else rc = launch_gain(c, root);
-    if (rc != MSCKF_OK) return rc;
+    GainSources src;                       // ONE source of rows: the merged root block, dense
+    src.first = rb + all.back().out_off; src.band = dc;
+    if (int rc = launch_gain_behind(c, src, gstream_ok(c, dc), rec)) return rc;
     hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, ptr<int>(c->dStatus) + 2, (int)total_accepted);   // (shared result)
     HIPCHK(c, hipGetLastError());
-    c->ran = true; c->ran_gain = true;
-    c->acc_override = total_accepted;
-    ++c->run_serial; c->run_pending = true;
+    finish_run(c, rec);
     return MSCKF_OK;
 }
 
@@ -3856,7 +3862,7 @@ int msckf_set_group_exchange(msckf_ctx* c, int on) {
     c->xchg = on != 0;
     c->have_features = false;             // the next msckf_set_features plans with the new layout
     c->plan_valid = false;
-    c->ran = false;
+    c->last.ran = false;
     return MSCKF_OK;
 }
 
@@ -3866,7 +3872,7 @@ int msckf_set_exchange_span(msckf_ctx* c, int32_t max_span) {
     c->have_features = false;
     c->plan_valid = false;
     c->x_plan_valid = false;
-    c->ran = false;
+    c->last.ran = false;
     return MSCKF_OK;
 }
 
@@ -3887,7 +3893,7 @@ int msckf_set_exchange_split(msckf_ctx* c, int32_t rows_per_record, int32_t rows
     c->have_features = false;             // the record layout changed: the next msckf_set_features plans afresh
     c->plan_valid = false;
     c->x_plan_valid = false;
-    c->ran = false;
+    c->last.ran = false;
     return MSCKF_OK;
 }
 
@@ -3976,7 +3982,7 @@ int msckf_exchange_split_rule(const msckf_ctx* c, int32_t N, int32_t F, const in
 
 int msckf_export_groups(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accepted) {
     if (!c || !dst) return MSCKF_ERR_ARG;
-    if (!c->ran) return MSCKF_ERR_STATE;
+    if (!c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = msckf_group_record_doubles(c) * 8;
     if (c->F == 0 || (c->root < 0 && !rem_in_record(c))) {       // no tracks in this shard: all flags 0
@@ -3987,7 +3993,7 @@ int msckf_export_groups(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_acce
         return MSCKF_OK;
     }
     if (!c->xchg_planned) return MSCKF_ERR_STATE;     // tree plan (wide tracks, N > 37): use msckf_export_block
-    if (c->ran_gain) return MSCKF_ERR_STATE;           // records come out of msckf_run_compress (it also counts the accepted)
+    if (c->last.gain) return MSCKF_ERR_STATE;           // records come out of msckf_run_compress (it also counts the accepted)
     // the shard's accepted count already sits in the record (double N, k_count_accepted): the merging rank sums them
     HIPCHK(c, hipMemcpyAsync(dst, c->dRbuf.p, bytes, device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     if (n_accepted) {                                  // optional: costs a device-to-host copy of the gate results
@@ -4028,7 +4034,6 @@ int collect_masks(msckf_ctx* c, const double* recs, long long rec_stride, int n_
 
 int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int device_ptr, int32_t total_accepted, const uint8_t* flags) {
     if (!c || !records || n_rec < 1) return MSCKF_ERR_ARG;
-    MergeScope merge_scope(c);
     if (!c->have_state) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->N, dc = c->dc;
@@ -4043,18 +4048,7 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
     const size_t MSLOT = xs ? (size_t)SWEEP_MAX_W * 64 : XCHG_SLOT;
     const size_t o_rec = c->gather_off, o_mrg = o_rec + (size_t)n_rec * rec, o_root = o_mrg + (size_t)N * MSLOT;
     const size_t o_zero = o_root + (size_t)dc * (dc + 1), o_end = o_zero + 16;
-    const size_t need = (o_end + 16) * 8;
-    if (c->dRbuf.bytes < need) {          // grow, keeping the local plan's blocks
-        void* np = nullptr;
-        HIPCHK(c, hipMalloc(&np, need));
-        HIPCHK(c, hipMemset(np, 0, need));
-        if (c->dRbuf.p) {
-            HIPCHK(c, hipMemcpy(np, c->dRbuf.p, std::min(c->dRbuf.bytes, c->gather_off * 8), hipMemcpyDeviceToDevice));
-            HIPCHK(c, hipFree(c->dRbuf.p));
-        }
-        c->dRbuf.p = np; c->dRbuf.bytes = need;
-        c->x_plan_valid = false;
-    }
+    if (int rc = grow_workspace(c, (o_end + 16) * 8)) return rc;
     double* rb = ptr<double>(c->dRbuf);
     // records already in HBM are folded where they lie (sources are offsets from the workspace base, which may
     // point outside it); host records are staged behind the local plan
@@ -4062,20 +4056,20 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
     if (device_ptr) recs = static_cast<const double*>(records);
     else HIPCHK(c, hipMemcpyAsync(rb + o_rec, records, (size_t)n_rec * rec * 8, hipMemcpyHostToDevice, c->stream));
     const long long rec_base = (long long)(recs - rb);
-    // status words 1 and 4 are this merge's: nothing of the rank's own earlier batch may be read as its outcome
-    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 1, 0, 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 4, 0, 4, c->stream));
+    if (int rc = begin_merge(c)) return rc;
     // split records (msckf_set_exchange_split): their remainder rows are K6-K7's second source, collected into dRem; from
     // t2_early_min() row blocks on the update on them is a launch of its own on the second stream, beside the group folds
     // and the root sweep (as launch_gain_t2_early on one GPU), the update on the root starts from its P_out / dx
-    c->x_rem_merge = c->xsplit_rows > 0;
+    const bool x_rem = c->xsplit_rows > 0;
+    GainSources gsrc;                      // the merge's update: on the merged root block (set below) and the collected remainder rows
+    gsrc.band = XW; gsrc.two_sources_in_batch = x_rem;
     bool early = false;
-    if (c->x_rem_merge) {
+    if (x_rem) {
         if (!gstream_ok_dc(c, dc)) { c->last_error = "split records need the streamed K6-K7"; return MSCKF_ERR_STATE; }
         long long rows = (long long)n_rec * c->xsplit_rows;
         if (c->xsplit_total > 0) rows = std::min<long long>(rows, c->xsplit_total);
-        c->x_rem_blocks = (int)std::min<long long>(GS_MAX_NB2, (rows + 15) / 16);
-        early = c->x_rem_blocks >= t2_early_min();
+        gsrc.second = ptr<double>(c->dRem); gsrc.nb2 = (int)std::min<long long>(GS_MAX_NB2, (rows + 15) / 16); gsrc.nb2_dev = drem_count(c);
+        early = gsrc.nb2 >= t2_early_min();
     }
     // which groups does each record carry?  (N flags and the accepted count at the head of every record)
     std::vector<double> key((size_t)n_rec * N);
@@ -4087,7 +4081,6 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         hipLaunchKernelGGL(k_sum_record_counts, dim3(1), dim3(64), 0, c->stream, recs, (long long)rec, N, n_rec, ptr<int>(c->dStatus) + 2);
         HIPCHK(c, hipGetLastError());
         count_on_device = true;
-        total_accepted = -1;
     } else {
         std::vector<double> head((size_t)n_rec * (N + 1));
         HIPCHK(c, hipMemcpy2DAsync(head.data(), (size_t)(N + 1) * 8, recs, rec * 8, (size_t)(N + 1) * 8, n_rec,
@@ -4203,62 +4196,49 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         c->x_plan_valid = true;
     }
     if (c->x_snodes.empty()) early = false;          // (remainder rows alone: one launch on them, status word 0)
-    c->t2_early = early;
-    c->x_status1 = early; c->x_rem_last = c->x_rem_merge;
-    if (c->x_rem_merge) {
+    RunRecord run;
+    run.kind = RunKind::GroupMerge; run.gain = true;
+    run.acc = count_on_device ? AccSource::Word2 : AccSource::Fixed; run.accepted = total_accepted;
+    run.word1_ours = early; run.word4_ours = x_rem;
+    if (x_rem) {
         if (early) {
             hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, ptr<int>(c->dStatus) + 4, 1);
             HIPCHK(c, hipGetLastError());
         }
         RemCollectArgs ra{};
         ra.recs = recs; ra.rec_stride = (long long)rec; ra.rem_off = (long long)rec_rem_off(c); ra.rec_rows = c->xsplit_rows;
-        ra.n_rec = n_rec; ra.ld = dc + 1; ra.max_rows = 16 * c->x_rem_blocks;
+        ra.n_rec = n_rec; ra.ld = dc + 1; ra.max_rows = 16 * gsrc.nb2;
         ra.out = ptr<double>(c->dRem);
-        ra.nrows = reinterpret_cast<int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1));
+        ra.nrows = drem_count(c);
         ra.status = ptr<int>(c->dStatus);
         hipLaunchKernelGGL(k_rem_collect, dim3(n_rec + 1), dim3(256), 0, c->stream, ra);
         HIPCHK(c, hipGetLastError());
         if (early) {
             HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
             HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-            if (int rce = launch_gain_t2_early(c, c->stream2)) return rce;
-            {   // MSCKF_DEBUG_FAKE_TIMEOUT=1 (tests): the first early update of a merge reads as timed out
-                static const bool fake = [] { const char* e = std::getenv("MSCKF_DEBUG_FAKE_TIMEOUT"); return e && std::atoi(e) == 1; }();
-                if (fake && !c->fake_timeout_done) {
-                    c->fake_timeout_done = true;
-                    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream2, ptr<int>(c->dStatus) + 1, 2);
-                    HIPCHK(c, hipGetLastError());
-                }
+            if (int rce = launch_gain_t2_early(c, gsrc, c->stream2)) return rce;
+            if (take_fake_timeout(c)) {
+                hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream2, ptr<int>(c->dStatus) + 1, 2);
+                HIPCHK(c, hipGetLastError());
             }
             HIPCHK(c, hipEventRecord(c->ev_rem, c->stream2));
+            gsrc.second = nullptr; gsrc.nb2 = 0; gsrc.nb2_dev = nullptr;
+            gsrc.start_from_result = true;
         }
     }
-    if (c->x_snodes.empty() && c->x_rem_merge) {     // no triangle anywhere, remainder rows only: K6-K7 on them alone
-        ++c->gs_epoch;
-        GStreamArgs ga;
-        fill_gstream_args(c, ga, nullptr, dc, false);
-        launch_gain_dense_rows(c, ga, c->stream);
-        HIPCHK(c, hipGetLastError());
-        if (int rcm = collect_masks(c, recs, (long long)rec, n_rec)) return rcm;
-        c->ran = true; c->ran_gain = true;
-        c->acc_override = total_accepted;
-        c->acc_from_dev = count_on_device;
-        ++c->run_serial; c->run_pending = true;
-        return MSCKF_OK;
-    }
-    if (c->x_snodes.empty()) {            // no shard has a track: nothing to update
+    const int nb = (int)c->snodes.size();
+    if (c->x_snodes.empty() && x_rem) {   // no triangle anywhere, remainder rows only: K6-K7 on them alone
+        gsrc.band = dc;
+        if (int rcd = launch_gain_dense_rows(c, gsrc, c->stream)) return rcd;
+    } else if (c->x_snodes.empty()) {     // no shard has a track: nothing to update
         if (!count_on_device) {
             hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, ptr<int>(c->dStatus) + 2, 0);
             HIPCHK(c, hipGetLastError());
         }
-        if (int rcm = collect_masks(c, recs, (long long)rec, n_rec)) return rcm;
-        c->ran = true; c->ran_gain = false; c->acc_override = 0; c->acc_from_dev = false;
-        ++c->run_serial; c->run_pending = true;
-        return MSCKF_OK;
-    }
-    const int nb = (int)c->snodes.size();
-    if (xmode > 0) {
+        run.gain = false; run.acc = AccSource::Fixed; run.accepted = 0;
+    } else if (xmode > 0) {
         // ring-buffered sweeps (N > 37 or tracks of 11-15 slots): cross-rank group merges in one launch, then the root
+        gsrc.first = rb + c->x_root_off;
         int ms = 0;
         for (int i = 0; i < c->x_n_merges; ++i) ms = std::max(ms, c->x_snodes[i].nsteps);
         const int rs = c->x_snodes.back().nsteps;
@@ -4272,58 +4252,49 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         }
         HIPCHK(c, hipGetLastError());
         if (early) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));      // (its P_out / dx are what the update below starts from)
-        if (c->x_rem_merge && !fused && !gstream_ok(c, XW)) { c->last_error = "split records need the streamed K6-K7"; return MSCKF_ERR_STATE; }
+        if (x_rem && !fused && !gstream_ok(c, XW)) { c->last_error = "split records need the streamed K6-K7"; return MSCKF_ERR_STATE; }
         int rcg;
-        if (fused && xmode == 1) rcg = launch_root_and_gain_w<4>(c, nb + c->x_n_merges, rs, WS_RC_LOG2_4, rb + c->x_zero_off, rb + c->x_root_off, XW);
-        else if (fused) rcg = launch_root_and_gain_w<6>(c, nb + c->x_n_merges, rs, WS_RC_LOG2_6, rb + c->x_zero_off, rb + c->x_root_off, XW);
-        else if (gstream_ok(c, XW)) rcg = launch_gain_stream(c, rb + c->x_root_off, XW);
-        else rcg = launch_gain(c, rb + c->x_root_off);
+        if (fused && xmode == 1) rcg = launch_root_and_gain_w<4>(c, nb + c->x_n_merges, rs, WS_RC_LOG2_4, rb + c->x_zero_off, gsrc);
+        else if (fused) rcg = launch_root_and_gain_w<6>(c, nb + c->x_n_merges, rs, WS_RC_LOG2_6, rb + c->x_zero_off, gsrc);
+        else rcg = launch_gain_behind(c, gsrc, gstream_ok(c, XW), run);
         if (rcg != MSCKF_OK) return rcg;
-        if (int rcm = collect_masks(c, recs, (long long)rec, n_rec)) return rcm;
-        c->ran = true; c->ran_gain = true;
-        c->acc_override = total_accepted;
-        c->acc_from_dev = count_on_device;
-        ++c->run_serial; c->run_pending = true;
-        return MSCKF_OK;
-    }
-    SweepArgs a{};
-    a.nodes = ptr<SweepNode>(c->dSweepNodes);
-    a.folds = ptr<SweepFold>(c->dSweepFolds);
-    a.rbuf = rb;
-    a.stamps = nullptr;
-    a.zero = rb + c->x_zero_off;
-    const dim3 block(64 * SWEEP_NW * SWEEP_WPF);
-    const bool fused = root_gain_ok(c, XW) && !c->x_root_flush.empty() && !early;
-    const bool ride_on = fused && c->x_streamed;
-    if (c->x_n_merges > 0 && !ride_on) {
-        a.node_base = nb;
-        hipLaunchKernelGGL((k_sweep<SWEEP_NW, SWEEP_WPF>), dim3(c->x_n_merges), block,
-                           sweep_lds_bytes(SWEEP_MAX_W, SWEEP_NW, SWEEP_WPF), c->stream, a);
-    }
-    a.node_base = nb + c->x_n_merges;
-    int rc;
-    if (fused) {
-        MergeRide ride{};
-        if (ride_on) {
-            ride = MergeRide{nb, c->x_n_merges, SWEEP_NW, c->x_root_n_gate, ptr<int>(c->dXRootFlush) + c->x_mflush_at, 0};
-            for (int i = 0; i < c->x_n_merges; ++i)
-                ride.lds = std::max(ride.lds, sweep_lds_bytes_fl(c->x_snodes[i].wtot, SWEEP_NW, c->x_snodes[i].nsteps));
-        }
-        rc = launch_root_and_gain(c, a, dc, c->x_snodes.back().nsteps, ptr<int>(c->dXRootFlush), rb + c->x_root_off, XW, ride_on ? &ride : nullptr);
     } else {
-        hipLaunchKernelGGL((k_sweep<SWEEP_NW, SWEEP_WPF, SWEEP_P2P>), dim3(1), block, sweep_lds_bytes(dc, SWEEP_NW, SWEEP_WPF), c->stream, a);
-        HIPCHK(c, hipGetLastError());
-        if (early) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));      // (its P_out / dx are what the update below starts from)
-        if (c->x_rem_merge && !gstream_ok(c, XW)) { c->last_error = "split records need the streamed K6-K7"; return MSCKF_ERR_STATE; }
-        if (gstream_ok(c, XW)) rc = launch_gain_stream(c, rb + c->x_root_off, XW);
-        else rc = launch_gain(c, rb + c->x_root_off);
+        gsrc.first = rb + c->x_root_off;
+        SweepArgs a{};
+        a.nodes = ptr<SweepNode>(c->dSweepNodes);
+        a.folds = ptr<SweepFold>(c->dSweepFolds);
+        a.rbuf = rb;
+        a.stamps = nullptr;
+        a.zero = rb + c->x_zero_off;
+        const dim3 block(64 * SWEEP_NW * SWEEP_WPF);
+        const bool fused = root_gain_ok(c, XW) && !c->x_root_flush.empty() && !early;
+        const bool ride_on = fused && c->x_streamed;
+        if (c->x_n_merges > 0 && !ride_on) {
+            a.node_base = nb;
+            hipLaunchKernelGGL((k_sweep<SWEEP_NW, SWEEP_WPF>), dim3(c->x_n_merges), block,
+                               sweep_lds_bytes(SWEEP_MAX_W, SWEEP_NW, SWEEP_WPF), c->stream, a);
+        }
+        a.node_base = nb + c->x_n_merges;
+        int rc;
+        if (fused) {
+            MergeRide ride{};
+            if (ride_on) {
+                ride = MergeRide{nb, c->x_n_merges, SWEEP_NW, c->x_root_n_gate, ptr<int>(c->dXRootFlush) + c->x_mflush_at, 0};
+                for (int i = 0; i < c->x_n_merges; ++i)
+                    ride.lds = std::max(ride.lds, sweep_lds_bytes_fl(c->x_snodes[i].wtot, SWEEP_NW, c->x_snodes[i].nsteps));
+            }
+            rc = launch_root_and_gain(c, a, dc, c->x_snodes.back().nsteps, ptr<int>(c->dXRootFlush), gsrc, ride_on ? &ride : nullptr);
+        } else {
+            hipLaunchKernelGGL((k_sweep<SWEEP_NW, SWEEP_WPF, SWEEP_P2P>), dim3(1), block, sweep_lds_bytes(dc, SWEEP_NW, SWEEP_WPF), c->stream, a);
+            HIPCHK(c, hipGetLastError());
+            if (early) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rem, 0));      // (its P_out / dx are what the update below starts from)
+            if (x_rem && !gstream_ok(c, XW)) { c->last_error = "split records need the streamed K6-K7"; return MSCKF_ERR_STATE; }
+            rc = launch_gain_behind(c, gsrc, gstream_ok(c, XW), run);
+        }
+        if (rc != MSCKF_OK) return rc;
     }
-    if (rc != MSCKF_OK) return rc;
     if (int rcm = collect_masks(c, recs, (long long)rec, n_rec)) return rcm;
-    c->ran = true; c->ran_gain = true;
-    c->acc_override = total_accepted;
-    c->acc_from_dev = count_on_device;
-    ++c->run_serial; c->run_pending = true;
+    finish_run(c, run);
     return MSCKF_OK;
 }
 }  // namespace
@@ -4414,7 +4385,7 @@ int msckf_comm_get(msckf_ctx* c, void* dst_host, const void* src_device, size_t 
 
 int msckf_export_result(msckf_ctx* c, void* dx_dst, void* P_dst, int device_ptr) {
     if (!c) return MSCKF_ERR_ARG;
-    if (!c->ran || !c->ran_gain) return MSCKF_ERR_STATE;
+    if (!c->last.ran || !c->last.gain) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t d = c->d;
     const hipMemcpyKind kind = device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -4449,7 +4420,7 @@ int msckf_set_exchange_mask(msckf_ctx* c, int32_t n_shards, const int32_t* bound
     c->have_features = false;             // the record layout changed: the next msckf_set_features plans afresh
     c->plan_valid = false;
     c->x_plan_valid = false;
-    c->ran = false;
+    c->last.ran = false;
     const size_t total = n_shards > 0 ? (size_t)bounds[n_shards] : 0;
     if (total > c->res_mask_cap) {        // the result range grows: nothing may be in flight on it
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4487,18 +4458,11 @@ int msckf_get_shared_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* ac
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int status[5];
     std::memcpy(status, c->hRes, 20);
-    const int dc = c->dc;
-    // (as launch_gain decides; k_gain_stream -- dtype f64 -- uses the first status word only)
-    const bool blocked = !(c->gs_enabled && (dc + 15) / 16 + 1 <= GS_MAX_NS) &&
-                         dc > 4 * CHOL_TILE_MAX_NT && dc <= 2 * GAIN_BLK && dc - GAIN_BLK >= 4;
+    // The other ranks have no record of the merge: what it launched travels in the range.  The accepted count is status word 2;
+    // word 4, which every merge zeroes or writes: bit 0 -- a launch of the merge, the early update on the remainder rows, wrote
+    // word 1; bit 1 -- the records held more remainder rows than the merge takes.
     const int n_acc = status[2];
-    int rc = (n_acc <= 0) ? MSCKF_NOOP : MSCKF_OK;
-    // (status word 4, written by merges of split records: bit 0 -- a launch of the merge, the early update on the remainder rows,
-    //  wrote word 1; bit 1 -- the records held more remainder rows than the merge takes)
-    const bool word1 = blocked || (status[4] & 1);
-    if (rc == MSCKF_OK && (status[0] != 0 || (word1 && status[1] != 0)))
-        rc = (status[0] == 2 || ((status[4] & 1) && status[1] == 2)) ? MSCKF_ERR_HIP : MSCKF_ERR_NOT_SPD;
-    if (rc == MSCKF_OK && (status[4] & 2)) rc = MSCKF_ERR_STATE;
+    const int rc = outcome_rc(c, decode_outcome(true, gain_is_blocked(c->gs_enabled, c->dc) || (status[4] & 1), true, n_acc, status));
     const char* hres = static_cast<const char*>(c->hRes);
     if (dx) {
         if (rc == MSCKF_OK) std::memcpy(dx, hres + c->res_dx_off, d * 8);
@@ -4524,7 +4488,7 @@ int msckf_get_shared_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* ac
 }
 
 int msckf_debug_gate(msckf_ctx* c, double* gamma, int32_t* qdim) {
-    if (!c || !c->ran) return MSCKF_ERR_STATE;
+    if (!c || !c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<double> g(c->F);
@@ -4541,7 +4505,7 @@ int msckf_debug_gate(msckf_ctx* c, double* gamma, int32_t* qdim) {
 }
 
 int msckf_debug_compressed(msckf_ctx* c, double* T, double* rn) {
-    if (!c || !c->ran) return MSCKF_ERR_STATE;
+    if (!c || !c->last.ran) return MSCKF_ERR_STATE;
     // split long tracks: K6-K7 took two sources of rows -- the band root and the remainder blocks' rows (as they are, or the root
     // of their own tree).  For this diagnostic ONE [T | r_n]: the Householder QR of both stacked, on the host.
     const bool tops = c->wide_active && !c->rem_direct && !c->rtops.empty();

@@ -203,6 +203,38 @@ def test_failed_early_update_of_a_sharded_merge():
         t._split_merge(e, good, partition_features(good.view_ptr, 4), _ref(good, ("good", bad.N), False)[2])
 
 
+def test_root_block_merge_behind_a_failed_run():
+    """A failed early update leaves status word 1 = 1 on the device; a root-block merge on the same engine (one source of rows,
+    nothing of it writes word 1) is then read by msckf_commit_covariance ALONE -- the reader that does its own read-back meets
+    the record of a run of another kind -- and, the same sequence again, by msckf_get_result: status 0 and the oracle's update."""
+    from msckf_amd.api import UpdateEngine
+    bad = _batch("early")
+    good = synth.make_problem(30, 64, 6, seed=1)
+    ref = oracle.update(good, dense_noise=False)
+    assert good.N == 30 and ref["status"] == 0
+    with UpdateEngine(max_clones=max(bad.N, good.N), max_features=400, max_track=30) as eng:     # (the failing batch has 34 clones)
+        for reader in ("commit", "result"):
+            eng.set_rem_direct_rows(-1)
+            eng.load(bad)
+            eng.run()
+            assert _raw_result(eng)[0] == ERR_NOT_SPD
+            eng.load(good)
+            eng.run_compress()
+            blk, n_acc = eng.export_block()
+            assert n_acc == int(ref["accepted"].sum())
+            eng.merge_gain(blk[None], n_acc)
+            if reader == "commit":
+                assert eng._lib.msckf_commit_covariance(eng._h) == 0
+                e_P = rel_err(eng.covariance(), ref["P_new"])
+                print("commit", e_P, flush=True)
+                assert e_P < TOL
+            else:
+                res = eng.result()
+                e_dx, e_P = rel_err(res.dx, ref["dx"]), rel_err(res.P_new, ref["P_new"])
+                print("result", res.status, e_dx, e_P, flush=True)
+                assert res.status == 0 and e_dx < TOL and e_P < TOL
+
+
 _CHILD = r"""
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r)

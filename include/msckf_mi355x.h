@@ -72,6 +72,9 @@ extern "C" {
 #define MSCKF_DTYPE_F32 1
 
 #define MSCKF_MAX_TRACK 31          /* views per feature (2M+1 rows fit one wavefront)      */
+#define MSCKF_MAX_TRACK_ROW 32      /* views a row of the track store may hold: a track of MSCKF_MAX_TRACK views can take
+                                       the newest clone's view (msckf_tracks_frame); a batch track still holds at most
+                                       MSCKF_MAX_TRACK                                        */
 
 typedef struct msckf_ctx msckf_ctx;
 
@@ -80,7 +83,8 @@ typedef struct msckf_config {
     int32_t device;                 /* HIP device ordinal                                   */
     int32_t max_clones;             /* capacity: N  (<= 221, else MSCKF_ERR_ARG)            */
     int32_t max_features;           /* capacity: F                                          */
-    int32_t max_track;              /* capacity: M  (<= MSCKF_MAX_TRACK)                    */
+    int32_t max_track;              /* capacity: M  (<= MSCKF_MAX_TRACK; MSCKF_MAX_TRACK_ROW gives the track store
+                                       rows of that many views, the batch limit stays MSCKF_MAX_TRACK) */
     int32_t leaf_rows;              /* 0 = default; target stacked rows per QR leaf         */
     int32_t merge_arity;            /* 0 = default; max children per QR tree node           */
     int32_t flags;                  /* MSCKF_FLAG_*; 0 = defaults                           */
@@ -334,6 +338,41 @@ int msckf_tracks_count(msckf_ctx* ctx, int32_t* n_tracks, int32_t* n_views);
 /* The ids of the tracks the last msckf_remove_clones deleted (left without a view): up to `cap` of them into ids;
  * returns how many there were (>= 0). */
 int msckf_tracks_dropped(msckf_ctx* ctx, int32_t* ids, int32_t cap);
+
+/* ---- frame intake on the store: test the matches, append, keep the counters ---- *
+ * MSCKF.add_camera_measurements :332-438 with the matcher's output as input: the listed (track id, keypoint, score) pairs
+ * are tested against every stored view of their track (the tests of msckf_run_associate) with the RESIDENT poses -- the
+ * newest clone is slot N - 1, so the call is correct straight behind msckf_augment_imu or msckf_commit_inject --, the
+ * pairs that pass are appended as msckf_tracks_observe appends them (the stored bits are equal) and unknown ids create
+ * tracks.  result[n]: 0 appended (tracked_for += 1, lost_for = 0, :411-412), 1 / 2 failed the epipolar / homography test
+ * (nothing appended, lost_for += 1, :400), 4 created (tracked_for = 1, lost_for = 0); 3 is not used, as the codes are
+ * msckf_run_associate's.  fail_view[n] (nullable): the first view that failed, -1.  Every stored track that is not listed
+ * gets lost_for += 1 (:438).  Blocking: the store's integer mirror needs the results.  The reference's two early returns
+ * (:286 no clone of the IMU's id, :320 no previous descriptors) are the caller's: do not call then.
+ * The counters lost_for_n_frames / tracked_for_n_frames live beside the mirror, two ints per track: msckf_tracks_observe
+ * counts as an append for the listed tracks and leaves the others alone, msckf_tracks_load neither reads nor writes them,
+ * they die with the track, msckf_tracks_reset and msckf_set_state clear them, msckf_remove_clones leaves them alone.
+ * Errors, nothing changed: MSCKF_ERR_STATE when N = 0; MSCKF_ERR_DUP_SLOT for an id listed twice or a track that already
+ * has a view of the newest clone; MSCKF_ERR_ARG for a negative id, a non-finite keypoint, a singular K, more fresh ids than
+ * free rows, or a listed known track that already holds max_track views. */
+typedef struct msckf_frame_params {
+    double K[9];                    /* intrinsics, row-major (the context only holds K^-1)            */
+    double epipolar_threshold;      /* MSCKFParameters.epipolar_rejection_threshold                   */
+    double homography_threshold;    /* MSCKFParameters.homography_rejection_threshold                 */
+} msckf_frame_params;
+int msckf_tracks_frame(msckf_ctx* ctx, const msckf_frame_params* params, int32_t n, const int32_t* ids,
+                       const double* uv /*2n*/, const double* score /*n*/, uint8_t* result /*n*/, int32_t* fail_view /*n, nullable*/);
+/* msckf_tracks_load with the stored counters for every track (n_slots == 0: process_features' candidates, MSCKF.py:453) or
+ * every track with at least one view in one of the listed clone slots (both prune paths, :669-674, :726-731), in the
+ * order the tracks were created (the reference's dict order, :461, :670, :727).  *F_out tracks; their ids go to ids_out in
+ * that order: the input order of accepted[], flags[] and msckf_get_selection.  No candidate: as msckf_tracks_load(F = 0).
+ * MSCKF_ERR_ARG when there are more than `cap` of them (nothing loaded) or a slot is outside [0, N). */
+int msckf_tracks_load_where(msckf_ctx* ctx, int32_t n_slots, const int32_t* slots, int32_t* F_out, int32_t* ids_out, int32_t cap);
+/* The stored counters of the listed tracks (either output nullable).  An unknown id: MSCKF_ERR_ARG. */
+int msckf_tracks_counters(msckf_ctx* ctx, int32_t n, const int32_t* ids, int32_t* lost_for, int32_t* tracked_for);
+/* Views per clone slot, views[N]: number_of_features_per_camera of prune_poorest_camera_states (:712-716); a zero is a
+ * clone of get_cameras_without_features (:781-790). */
+int msckf_tracks_clone_views(msckf_ctx* ctx, int32_t* views /*N*/);
 
 /* ---- feature-sharded path (one context per GPU / rank) ------------------ *
  * Each rank holds a shard of the features and the full state.  It runs K1-K5

@@ -18,6 +18,7 @@ OK, NOOP = 0, 1
 ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOT_SPD, ERR_STATE, ERR_DUP_SLOT, ERR_COMM = -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
 MAX_TRACK = 31
+MAX_TRACK_ROW = 32      # MSCKF_MAX_TRACK_ROW: views a row of the track store may hold (a batch track: MAX_TRACK)
 
 # every symbol include/msckf_mi355x.h declares
 SYMBOLS = [
@@ -37,6 +38,7 @@ SYMBOLS = [
     "msckf_set_nominal", "msckf_get_nominal", "msckf_propagate_imu", "msckf_augment_imu", "msckf_commit_inject",
     "msckf_tracks_reset", "msckf_tracks_observe", "msckf_tracks_remove", "msckf_tracks_load", "msckf_tracks_get",
     "msckf_tracks_count", "msckf_tracks_dropped",
+    "msckf_tracks_frame", "msckf_tracks_load_where", "msckf_tracks_counters", "msckf_tracks_clone_views",
 ]
 
 
@@ -60,6 +62,10 @@ class Stats(C.Structure):
 class AssocParamsC(C.Structure):
     _fields_ = [("K", C.c_double * 9), ("R_cur", C.c_double * 9), ("t_cur", C.c_double * 3),
                 ("epipolar_threshold", C.c_double), ("homography_threshold", C.c_double)]
+
+
+class FrameParamsC(C.Structure):
+    _fields_ = [("K", C.c_double * 9), ("epipolar_threshold", C.c_double), ("homography_threshold", C.c_double)]
 
 
 class SelectParamsC(C.Structure):
@@ -221,7 +227,11 @@ def load():
     lib.msckf_tracks_get.argtypes = [vp, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]
     lib.msckf_tracks_count.argtypes = [vp, _ip, _ip]
     lib.msckf_tracks_dropped.argtypes = [vp, _ip, C.c_int32]
-    for name in ("reset", "observe", "remove", "load", "get", "count", "dropped"):
+    lib.msckf_tracks_frame.argtypes = [vp, C.POINTER(FrameParamsC), C.c_int32, _ip, _dp, _dp, _up, _ip]
+    lib.msckf_tracks_load_where.argtypes = [vp, C.c_int32, _ip, _ip, _ip, C.c_int32]
+    lib.msckf_tracks_counters.argtypes = [vp, C.c_int32, _ip, _ip, _ip]
+    lib.msckf_tracks_clone_views.argtypes = [vp, _ip]
+    for name in ("reset", "observe", "remove", "load", "get", "count", "dropped", "frame", "load_where", "counters", "clone_views"):
         getattr(lib, "msckf_tracks_" + name).restype = C.c_int
     lib.msckf_debug_split.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.msckf_debug_split.restype = C.c_int

@@ -94,8 +94,8 @@ class UpdateEngine:
         dtype: "f64" = the reference's arithmetic (parity 1e-8); "f32" = fp32 storage of the stacked system and
         the Joseph covariance update on the f32 matrix cores (BASELINE.json configs[4]; tolerance in DESIGN.md)."""
         self._lib = _ffi.load()
-        if max_track > _ffi.MAX_TRACK:
-            raise ValueError(f"max_track {max_track} > {_ffi.MAX_TRACK}")
+        if max_track > _ffi.MAX_TRACK_ROW:               # (MAX_TRACK + 1: rows of the track store only, a batch track holds MAX_TRACK)
+            raise ValueError(f"max_track {max_track} > {_ffi.MAX_TRACK_ROW}")
         if plan not in ("auto", "band", "tree"):
             raise ValueError("plan must be 'auto', 'band' or 'tree'")
         if dtype not in ("f64", "f32"):
@@ -446,10 +446,54 @@ class UpdateEngine:
                     allow_noop=False)
         self._F = int(i.size)
 
+    def tracks_frame(self, ids, uv, score, K, epipolar_threshold: float = 5.0, homography_threshold: float = 5.0):
+        """A frame's matches on the store (reference `MSCKF.py:332-438`): each (track id, keypoint, score) is tested against
+        every stored view of its track with the resident poses; those that pass are appended as `tracks_observe` would,
+        unknown ids create tracks, and the stored `lost_for` / `tracked_for` counters follow (unlisted tracks: lost + 1).
+        Returns (result (n,) uint8: 0 appended, 1 epipolar failure, 2 homography failure, 4 created; fail_view (n,)
+        int32).  Blocking."""
+        i, u, s = _ffi.i32(np.asarray(ids).reshape(-1)), _ffi.f64(uv).reshape(-1), _ffi.f64(score).reshape(-1)
+        if u.size != 2 * i.size or s.size != i.size:
+            raise ValueError("uv is (n, 2), score (n,)")
+        fp = _ffi.FrameParamsC()
+        fp.K = (C.c_double * 9)(*np.asarray(K, dtype=np.float64).reshape(9))
+        fp.epipolar_threshold, fp.homography_threshold = float(epipolar_threshold), float(homography_threshold)
+        n = int(i.size)
+        res, fv = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self._lib.msckf_tracks_frame(self._h, C.byref(fp), n, _ffi.iptr(i), _ffi.dptr(u), _ffi.dptr(s),
+                                                 _ffi.uptr(res), _ffi.iptr(fv)), allow_noop=False)
+        return res[:n].copy(), fv[:n].copy()
+
+    def load_tracks_where(self, slots=None) -> np.ndarray:
+        """`load_tracks` with the stored counters for every track (`slots` None or empty: `process_features`' candidates)
+        or every track with a view in one of the listed clone slots (the prune paths), in the order the tracks were
+        created.  Returns their ids: the input order of `accepted`, `flags` and `selection()`."""
+        sl = _ffi.i32(np.zeros(0) if slots is None else np.asarray(slots).reshape(-1))
+        cap = max(self.tracks_count()[0], 1)
+        ids, F = np.zeros(cap, dtype=np.int32), C.c_int32(0)
+        self._check(self._lib.msckf_tracks_load_where(self._h, int(sl.size), _ffi.iptr(sl), C.addressof(F), _ffi.iptr(ids), cap),
+                    allow_noop=False)
+        self._F = int(F.value)
+        return ids[:self._F].copy()
+
+    def tracks_counters(self, ids):
+        """(lost_for, tracked_for) of the listed tracks as the store keeps them."""
+        i = _ffi.i32(np.asarray(ids).reshape(-1))
+        lo, tr = np.zeros(max(i.size, 1), dtype=np.int32), np.zeros(max(i.size, 1), dtype=np.int32)
+        self._check(self._lib.msckf_tracks_counters(self._h, int(i.size), _ffi.iptr(i), _ffi.iptr(lo), _ffi.iptr(tr)),
+                    allow_noop=False)
+        return lo[:i.size].copy(), tr[:i.size].copy()
+
+    def tracks_clone_views(self) -> np.ndarray:
+        """Views per clone slot (`number_of_features_per_camera`, reference `MSCKF.py:712-716`); zero: a clone without features."""
+        out = np.zeros(max(self._N, 1), dtype=np.int32)
+        self._check(self._lib.msckf_tracks_clone_views(self._h, _ffi.iptr(out)), allow_noop=False)
+        return out[:self._N].copy()
+
     def track(self, track_id: int) -> dict:
         """One track as it stands on the device (waits for the stream): `slots, uv, dir, conf, line_base, idp_base,
         idp_m, idp_rho, anchor_slot` (-1 once the anchor clone was removed: the base is frozen)."""
-        V = _ffi.MAX_TRACK
+        V = _ffi.MAX_TRACK_ROW
         M, anchor = C.c_int32(0), C.c_int32(0)
         rho = C.c_double(0)
         slots = np.zeros(V, dtype=np.int32)

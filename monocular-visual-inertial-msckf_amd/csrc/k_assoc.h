@@ -33,6 +33,47 @@ __device__ __forceinline__ void mat3_mul(const double* A, const double* B, doubl
         for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
 }
 
+// One (match, earlier view) test: 0 passed, 1 epipolar failure, 2 homography failure.  (R1, t1): the earlier view's clone,
+// (R2, t2): the newest clone, f: the view's keypoint, m: the matched one.  Shared by k_assoc and k_track_frame (k_tracks.h).
+__device__ __forceinline__ int assoc_view_test(const double* K, const double* Kinv, const double* R1, const double* t1,
+                                               const double* R2, const double* t2, double fx, double fy, double mx, double my,
+                                               double thr_epipolar, double thr_homography) {
+    // T_12 = T_W_C1^-1 T_W_C2: R12 = R1^T R2, t12 = R1^T (t2 - t1)
+    double R12[9], t12[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R12[3 * i + j] = R1[i] * R2[j] + R1[3 + i] * R2[3 + j] + R1[6 + i] * R2[6 + j];
+        t12[i] = R1[i] * (t2[0] - t1[0]) + R1[3 + i] * (t2[1] - t1[1]) + R1[6 + i] * (t2[2] - t1[2]);
+    }
+    const double nt = sqrt(t12[0] * t12[0] + t12[1] * t12[1] + t12[2] * t12[2]);
+    if (nt < 0.01) {
+        double KR[9], H[9], KRt[9], Hi[9], R12t[9];
+        mat3_mul(K, R12, KR);
+        mat3_mul(KR, Kinv, H);                                         // H = K R12 K^-1
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) R12t[3 * i + j] = R12[3 * j + i];
+        mat3_mul(K, R12t, KRt);
+        mat3_mul(KRt, Kinv, Hi);                                       // H^-1 = K R12^T K^-1
+        const double a0 = Hi[0] * mx + Hi[1] * my + Hi[2], a1 = Hi[3] * mx + Hi[4] * my + Hi[5], a2 = Hi[6] * mx + Hi[7] * my + Hi[8];
+        const double b0 = H[0] * fx + H[1] * fy + H[2], b1 = H[3] * fx + H[4] * fy + H[5], b2 = H[6] * fx + H[7] * fy + H[8];
+        const double e1x = mx - a0 / a2, e1y = my - a1 / a2, e2x = fx - b0 / b2, e2y = fy - b1 / b2;
+        const double score = 0.5 * (sqrt(e1x * e1x + e1y * e1y) + sqrt(e2x * e2x + e2y * e2y));
+        return score > thr_homography ? 2 : 0;
+    }
+    // F = K^-T [t12]x R12 K^-1;  score = m^T F x1 = (K^-1 m)^T [t12]x R12 (K^-1 x1)
+    const double* Ki = Kinv;
+    const double m0 = Ki[0] * mx + Ki[1] * my + Ki[2], m1 = Ki[3] * mx + Ki[4] * my + Ki[5], m2 = Ki[6] * mx + Ki[7] * my + Ki[8];
+    const double x0 = Ki[0] * fx + Ki[1] * fy + Ki[2], x1 = Ki[3] * fx + Ki[4] * fy + Ki[5], x2 = Ki[6] * fx + Ki[7] * fy + Ki[8];
+    const double y0 = R12[0] * x0 + R12[1] * x1 + R12[2] * x2, y1 = R12[3] * x0 + R12[4] * x1 + R12[5] * x2,
+                 y2 = R12[6] * x0 + R12[7] * x1 + R12[8] * x2;
+    const double c0 = t12[1] * y2 - t12[2] * y1, c1 = t12[2] * y0 - t12[0] * y2, c2 = t12[0] * y1 - t12[1] * y0;   // t12 x y
+    const double score = m0 * c0 + m1 * c1 + m2 * c2;
+    return score > thr_epipolar ? 1 : 0;
+}
+
 __global__ __launch_bounds__(256) void k_assoc(AssocArgs p) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= p.F) return;
@@ -43,44 +84,9 @@ __global__ __launch_bounds__(256) void k_assoc(AssocArgs p) {
     const int v0 = p.view_ptr[f], v1 = p.view_ptr[f + 1];
     for (int o = v0; o < v1 && res == 0; ++o) {
         const int s = p.obs_slot[o];
-        const double* R1 = p.cam_R + 9 * s;
-        const double* t1 = p.cam_t + 3 * s;
-        const double fx = p.obs_uv[2 * o], fy = p.obs_uv[2 * o + 1];
-        // T_12 = T_W_C1^-1 T_W_C2: R12 = R1^T R2, t12 = R1^T (t2 - t1)
-        double R12[9], t12[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) R12[3 * i + j] = R1[i] * p.R2[j] + R1[3 + i] * p.R2[3 + j] + R1[6 + i] * p.R2[6 + j];
-            t12[i] = R1[i] * (p.t2[0] - t1[0]) + R1[3 + i] * (p.t2[1] - t1[1]) + R1[6 + i] * (p.t2[2] - t1[2]);
-        }
-        const double nt = sqrt(t12[0] * t12[0] + t12[1] * t12[1] + t12[2] * t12[2]);
-        if (nt < 0.01) {
-            double KR[9], H[9], KRt[9], Hi[9], R12t[9];
-            mat3_mul(p.K, R12, KR);
-            mat3_mul(KR, p.Kinv, H);                                   // H = K R12 K^-1
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) R12t[3 * i + j] = R12[3 * j + i];
-            mat3_mul(p.K, R12t, KRt);
-            mat3_mul(KRt, p.Kinv, Hi);                                 // H^-1 = K R12^T K^-1
-            const double a0 = Hi[0] * mx + Hi[1] * my + Hi[2], a1 = Hi[3] * mx + Hi[4] * my + Hi[5], a2 = Hi[6] * mx + Hi[7] * my + Hi[8];
-            const double b0 = H[0] * fx + H[1] * fy + H[2], b1 = H[3] * fx + H[4] * fy + H[5], b2 = H[6] * fx + H[7] * fy + H[8];
-            const double e1x = mx - a0 / a2, e1y = my - a1 / a2, e2x = fx - b0 / b2, e2y = fy - b1 / b2;
-            const double score = 0.5 * (sqrt(e1x * e1x + e1y * e1y) + sqrt(e2x * e2x + e2y * e2y));
-            if (score > p.thr_homography) { res = 2; fv = o - v0; }
-        } else {
-            // F = K^-T [t12]x R12 K^-1;  score = m^T F x1 = (K^-1 m)^T [t12]x R12 (K^-1 x1)
-            const double* Ki = p.Kinv;
-            const double m0 = Ki[0] * mx + Ki[1] * my + Ki[2], m1 = Ki[3] * mx + Ki[4] * my + Ki[5], m2 = Ki[6] * mx + Ki[7] * my + Ki[8];
-            const double x0 = Ki[0] * fx + Ki[1] * fy + Ki[2], x1 = Ki[3] * fx + Ki[4] * fy + Ki[5], x2 = Ki[6] * fx + Ki[7] * fy + Ki[8];
-            const double y0 = R12[0] * x0 + R12[1] * x1 + R12[2] * x2, y1 = R12[3] * x0 + R12[4] * x1 + R12[5] * x2,
-                         y2 = R12[6] * x0 + R12[7] * x1 + R12[8] * x2;
-            const double c0 = t12[1] * y2 - t12[2] * y1, c1 = t12[2] * y0 - t12[0] * y2, c2 = t12[0] * y1 - t12[1] * y0;   // t12 x y
-            const double score = m0 * c0 + m1 * c1 + m2 * c2;
-            if (score > p.thr_epipolar) { res = 1; fv = o - v0; }
-        }
+        const int code = assoc_view_test(p.K, p.Kinv, p.cam_R + 9 * s, p.cam_t + 3 * s, p.R2, p.t2, p.obs_uv[2 * o], p.obs_uv[2 * o + 1],
+                                         mx, my, p.thr_epipolar, p.thr_homography);
+        if (code) { res = (unsigned char)code; fv = o - v0; }
     }
     p.result[f] = res;
     p.fail_view[f] = fv;

@@ -3,6 +3,7 @@
 //   reference MSCKF.add_camera_measurements (src/msckf/MSCKF.py:403-411, :420-434)  -> k_track_observe
 //   the candidate set of MSCKF.get_valid_features / update (:458-495, :570-582)     -> k_track_emit
 //   MSCKF.remove_cameras' feature half (:760-779)                                   -> k_track_drop
+//   the per-view tests of a frame's matches and the append of those that pass (:332-438) -> k_track_frame
 //   the refresh of the inverse-depth point that persists (:484-488)                 -> k_track_writeback
 // Rows and positions are decided by the host's integer mirror (msckf_abi.hip) and passed in: no kernel here searches,
 // allocates or uses an atomic.  A line's base is the clone's own position array in the reference (:410, :430-431) and an
@@ -12,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "k_assoc.h"
 #include "k_select.h"
 
 namespace msckf {
@@ -43,30 +45,34 @@ struct TrackObsArgs {
     double Kinv[9];
 };
 
+// The store of one new view (shared by k_track_observe and k_track_frame: the stored bits are the same whoever appends).
+__device__ __forceinline__ void track_store_view(const TrackStore& s, const TrackObsRec& r, int slot, const double* R, const double* Kinv) {
+    const double ex = Kinv[0] * r.u + Kinv[1] * r.v + Kinv[2];            // Camera.inverse_project_point (Camera.py:30-36)
+    const double ey = Kinv[3] * r.u + Kinv[4] * r.v + Kinv[5];
+    const double ez = Kinv[6] * r.u + Kinv[7] * r.v + Kinv[8];
+    const double gx = R[0] * ex + R[1] * ey + R[2] * ez;                  // Ci2W, rotation only (:38-44)
+    const double gy = R[3] * ex + R[4] * ey + R[5] * ez;
+    const double gz = R[6] * ex + R[7] * ey + R[8] * ez;
+    const size_t e = (size_t)r.row * s.V + r.pos;
+    s.uv[2 * e] = r.u; s.uv[2 * e + 1] = r.v;
+    s.dir[3 * e] = gx; s.dir[3 * e + 1] = gy; s.dir[3 * e + 2] = gz;
+    s.conf[e] = r.score;
+    s.slot[e] = slot;
+    s.count[r.row] = r.pos + 1;
+    if (r.fresh) {                                                        // InverseDepthPoint(camera pose, W_v), geometry.py:53-59
+        const double gn = sqrt(gx * gx + gy * gy + gz * gz);
+        s.m[3 * (size_t)r.row] = gx / gn; s.m[3 * (size_t)r.row + 1] = gy / gn; s.m[3 * (size_t)r.row + 2] = gz / gn;
+        s.rho[r.row] = 0.1;
+        s.anchor[r.row] = slot;
+    }
+}
+
 // One lane per new view.
 __global__ __launch_bounds__(256) void k_track_observe(TrackObsArgs p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= p.n) return;
     const TrackObsRec r = p.rec[i];
-    const double ex = p.Kinv[0] * r.u + p.Kinv[1] * r.v + p.Kinv[2];      // Camera.inverse_project_point (Camera.py:30-36)
-    const double ey = p.Kinv[3] * r.u + p.Kinv[4] * r.v + p.Kinv[5];
-    const double ez = p.Kinv[6] * r.u + p.Kinv[7] * r.v + p.Kinv[8];
-    const double* R = p.R;
-    const double gx = R[0] * ex + R[1] * ey + R[2] * ez;                  // Ci2W, rotation only (:38-44)
-    const double gy = R[3] * ex + R[4] * ey + R[5] * ez;
-    const double gz = R[6] * ex + R[7] * ey + R[8] * ez;
-    const size_t e = (size_t)r.row * p.s.V + r.pos;
-    p.s.uv[2 * e] = r.u; p.s.uv[2 * e + 1] = r.v;
-    p.s.dir[3 * e] = gx; p.s.dir[3 * e + 1] = gy; p.s.dir[3 * e + 2] = gz;
-    p.s.conf[e] = r.score;
-    p.s.slot[e] = p.slot;
-    p.s.count[r.row] = r.pos + 1;
-    if (r.fresh) {                                                        // InverseDepthPoint(camera pose, W_v), geometry.py:53-59
-        const double gn = sqrt(gx * gx + gy * gy + gz * gz);
-        p.s.m[3 * (size_t)r.row] = gx / gn; p.s.m[3 * (size_t)r.row + 1] = gy / gn; p.s.m[3 * (size_t)r.row + 2] = gz / gn;
-        p.s.rho[r.row] = 0.1;
-        p.s.anchor[r.row] = p.slot;
-    }
+    track_store_view(p.s, r, p.slot, p.R, p.Kinv);
 }
 
 struct __attribute__((aligned(8))) TrackEmitRec {
@@ -173,6 +179,50 @@ __global__ __launch_bounds__(TRACK_THREADS) void k_track_drop(TrackDropArgs p) {
             p.s.anchor[row] = na;
         }
     }
+}
+
+// A frame's matches on the store (reference MSCKF.add_camera_measurements, :332-438): the association test of k_assoc.h of
+// every listed (track, keypoint) pair against the track's stored views, with the newest clone's pose read where it is
+// resident, and the append of the pairs that pass.
+struct TrackFrameArgs {
+    TrackStore s;
+    const TrackObsRec* rec;       // [n] (pinned host image); pos = the row's view count, the position an append takes
+    int n, slot;                  // slot: the newest clone's, N - 1
+    const double* cam_R;          // [N][9], [N][3] resident clone poses
+    const double* cam_t;
+    double K[9], Kinv_test[9];    // the intrinsics and their inverse as the tests form it (MSCKF.py:345)
+    double Kinv[9];               // the context's K^-1: the stored direction
+    double thr_epipolar, thr_homography;
+    int* fail_view;               // [n] (pinned host memory) first view that failed, -1
+    unsigned char* result;        // [n] (pinned host memory) 0 appended, 1 epipolar failure, 2 homography failure, 4 created
+};
+
+// One 32-lane group per pair; lane v tests stored view v (a tested row holds at most 31).  The group's half of the
+// wavefront's ballot gives the first failing view, where the reference breaks (:369, :390).  Lane 0 appends: position
+// `pos` is read by no lane (v < pos), and every pair has a row of its own.
+__global__ __launch_bounds__(TRACK_THREADS) void k_track_frame(TrackFrameArgs p) {
+    const int v = threadIdx.x & 31;
+    const int g = blockIdx.x * (TRACK_THREADS / 32) + (threadIdx.x >> 5);
+    const bool live = g < p.n;
+    TrackObsRec r{};
+    if (live) r = p.rec[g];
+    const int M = (live && !r.fresh) ? r.pos : 0;
+    const double* R2 = p.cam_R + 9 * (size_t)p.slot;
+    const double* t2 = p.cam_t + 3 * (size_t)p.slot;
+    int code = 0;
+    if (v < M) {
+        const size_t e = (size_t)r.row * p.s.V + v;
+        const int sl = p.s.slot[e];
+        code = assoc_view_test(p.K, p.Kinv_test, p.cam_R + 9 * (size_t)sl, p.cam_t + 3 * (size_t)sl, R2, t2, p.s.uv[2 * e], p.s.uv[2 * e + 1],
+                               r.u, r.v, p.thr_epipolar, p.thr_homography);
+    }
+    const unsigned long long bf = __ballot(code != 0), bh = __ballot(code == 2);
+    const unsigned fails = (unsigned)(bf >> (threadIdx.x & 32)), homs = (unsigned)(bh >> (threadIdx.x & 32));
+    if (!live || v != 0) return;
+    const int first = fails ? __ffs(fails) - 1 : -1;
+    p.fail_view[g] = first;
+    p.result[g] = r.fresh ? 4 : first < 0 ? 0 : ((homs >> first) & 1u) ? 2 : 1;
+    if (first < 0) track_store_view(p.s, r, p.slot, R2, p.Kinv);
 }
 
 // Behind k_select: the refreshed inverse-depth points go back to their rows (the reference's refresh persists).

@@ -290,6 +290,7 @@ struct msckf_ctx {
     long hp_calls = 0;
     // capacities
     int maxN = 0, maxF = 0, maxM = 0;
+    int maxV = 0;                         // views a row of the track store holds: max_track, which may be MSCKF_MAX_TRACK + 1 (a batch track: maxM)
     // current problem
     int N = 0, d = 0, dc = 0, F = 0, sumM = 0, Mmax = 0;
     bool have_state = false, have_features = false;
@@ -488,11 +489,14 @@ struct msckf_ctx {
     TrackStore trk{};
     bool trk_ready = false;
     std::vector<int> trk_id, trk_M, trk_anchor, trk_slots;   // per row: id (-1: free), views, anchor slot (-1: frozen), [row][V] slots
+    std::vector<int> trk_lost, trk_tracked;                  // per row: lost_for_n_frames / tracked_for_n_frames (MSCKF.py:400, :411-412, :438)
+    std::vector<long long> trk_seq;                          // per row: when the track was created (rows are recycled; the reference's dict order)
+    long long trk_next_seq = 0;
     std::vector<int> trk_free, trk_dropped;                  // free rows (a stack); ids the last msckf_remove_clones deleted
     std::unordered_map<int, int> trk_row_of;                 // id -> row
     long long trk_views = 0;
     bool batch_from_store = false;        // the current batch came through msckf_tracks_load: msckf_run_select writes refreshed points back
-    PinStage trk_obs_stage, trk_load_stage;
+    PinStage trk_obs_stage, trk_load_stage, trk_frame_stage;
     long fetched_serial = -1;             // the run whose return code msckf_get_result derived last ...
     int fetched_rc = 0;                   // ... and that code: msckf_commit_covariance need not read the gate results again
 };
@@ -2128,6 +2132,9 @@ void tracks_clear(msckf_ctx* c) {
     const int T = c->maxF;
     std::fill(c->trk_id.begin(), c->trk_id.end(), -1);
     std::fill(c->trk_M.begin(), c->trk_M.end(), 0);
+    std::fill(c->trk_lost.begin(), c->trk_lost.end(), 0);
+    std::fill(c->trk_tracked.begin(), c->trk_tracked.end(), 0);
+    c->trk_next_seq = 0;
     c->trk_free.resize(T);
     for (int r = 0; r < T; ++r) c->trk_free[r] = T - 1 - r;         // row 0 goes out first
 }
@@ -2135,7 +2142,7 @@ void tracks_clear(msckf_ctx* c) {
 // capacity max_features tracks x max_track views, allocated on first use
 int tracks_ensure(msckf_ctx* c) {
     if (c->trk_ready) return MSCKF_OK;
-    const size_t T = c->maxF, V = c->maxM, TV = T * V;
+    const size_t T = c->maxF, V = c->maxV, TV = T * V;
     const size_t o_uv = 0, o_dir = o_uv + TV * 16, o_conf = o_dir + TV * 24, o_m = o_conf + TV * 8, o_rho = o_m + T * 24;
     const size_t o_frozen = o_rho + T * 8, o_slot = o_frozen + T * 24, o_anchor = o_slot + TV * 4, o_count = o_anchor + T * 4;
     if (int rc = ensure(c, c->dTrk, o_count + T * 4, true)) return rc;
@@ -2148,6 +2155,7 @@ int tracks_ensure(msckf_ctx* c) {
     s.slot = reinterpret_cast<int*>(b + o_slot); s.anchor = reinterpret_cast<int*>(b + o_anchor);
     s.count = reinterpret_cast<int*>(b + o_count); s.V = (int)V;
     c->trk_id.assign(T, -1); c->trk_M.assign(T, 0); c->trk_anchor.assign(T, -1); c->trk_slots.assign(TV, 0);
+    c->trk_lost.assign(T, 0); c->trk_tracked.assign(T, 0); c->trk_seq.assign(T, 0);
     c->trk_ready = true;
     tracks_clear(c);
     return MSCKF_OK;
@@ -2157,6 +2165,7 @@ inline void tracks_free_row(msckf_ctx* c, int row) {
     c->trk_row_of.erase(c->trk_id[row]);
     c->trk_views -= c->trk_M[row];
     c->trk_id[row] = -1; c->trk_M[row] = 0;
+    c->trk_lost[row] = c->trk_tracked[row] = 0;                     // the counters die with the track
     c->trk_free.push_back(row);
     c->batch_from_store = false;          // (the row may be handed out again: a loaded batch no longer writes refreshed points back)
 }
@@ -2187,11 +2196,22 @@ int launch_track_emit(msckf_ctx* c, const TrackEmitSrc* src, int F, int sumM, co
     return stage_release(c, c->trk_load_stage);
 }
 
+// inverse of K as the reference forms it for the association tests (np.linalg.inv(self.K), MSCKF.py:345); false: singular
+bool assoc_kinv(const double* K, double* Kinv) {
+    const double det = K[0] * (K[4] * K[8] - K[5] * K[7]) - K[1] * (K[3] * K[8] - K[5] * K[6]) + K[2] * (K[3] * K[7] - K[4] * K[6]);
+    if (det == 0.0) return false;
+    const double id = 1.0 / det;
+    Kinv[0] = (K[4] * K[8] - K[5] * K[7]) * id; Kinv[1] = (K[2] * K[7] - K[1] * K[8]) * id; Kinv[2] = (K[1] * K[5] - K[2] * K[4]) * id;
+    Kinv[3] = (K[5] * K[6] - K[3] * K[8]) * id; Kinv[4] = (K[0] * K[8] - K[2] * K[6]) * id; Kinv[5] = (K[2] * K[3] - K[0] * K[5]) * id;
+    Kinv[6] = (K[3] * K[7] - K[4] * K[6]) * id; Kinv[7] = (K[1] * K[6] - K[0] * K[7]) * id; Kinv[8] = (K[0] * K[4] - K[1] * K[3]) * id;
+    return true;
+}
+
 // msckf_remove_clones on a context whose store holds tracks (reference MSCKF.py:760-779): drop[s] != 0 for the clones that go
 int tracks_drop_clones(msckf_ctx* c, const std::vector<char>& drop) {
     c->trk_dropped.clear();
     if (!c->trk_ready || c->trk_row_of.empty()) return MSCKF_OK;
-    const int N = c->N, V = c->maxM;
+    const int N = c->N, V = c->maxV;
     TrackDropArgs a{};
     for (int s = 0, k = 0; s < N; ++s) a.remap[s] = drop[s] ? (short)-1 : (short)k++;
     std::vector<int> rows;
@@ -2243,7 +2263,7 @@ int msckf_device_count(void) {
 
 int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     if (!out || !cfg || cfg->abi_version != MSCKF_ABI_VERSION) return MSCKF_ERR_ARG;
-    if (cfg->max_track < 1 || cfg->max_track > MSCKF_MAX_TRACK || cfg->max_clones < 1 || cfg->max_features < 0)
+    if (cfg->max_track < 1 || cfg->max_track > MSCKF_MAX_TRACK_ROW || cfg->max_clones < 1 || cfg->max_features < 0)
         return MSCKF_ERR_ARG;
     if (cfg->dtype != MSCKF_DTYPE_F64 && cfg->dtype != MSCKF_DTYPE_F32) return MSCKF_ERR_ARG;
     int n = 0;
@@ -2251,7 +2271,7 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     msckf_ctx* c = new msckf_ctx();
     c->cfg = *cfg;
     c->device = cfg->device;
-    c->maxN = cfg->max_clones; c->maxF = cfg->max_features; c->maxM = cfg->max_track;
+    c->maxN = cfg->max_clones; c->maxF = cfg->max_features; c->maxM = std::min<int>(cfg->max_track, MSCKF_MAX_TRACK); c->maxV = cfg->max_track;
     if (hipSetDevice(c->device) != hipSuccess) { delete c; return MSCKF_ERR_NO_DEVICE; }
     hipDeviceProp_t prop{};
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) { delete c; return MSCKF_ERR_NO_DEVICE; }
@@ -2453,7 +2473,7 @@ void msckf_destroy(msckf_ctx* c) {
     if (c->hPlan) (void)hipHostFree(c->hPlan);
     if (c->ev_state) (void)hipEventDestroy(c->ev_state);
     if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
-    for (PinStage* ps : {&c->trk_obs_stage, &c->trk_load_stage}) {
+    for (PinStage* ps : {&c->trk_obs_stage, &c->trk_load_stage, &c->trk_frame_stage}) {
         if (ps->ev) (void)hipEventDestroy(ps->ev);
         if (ps->p) (void)hipHostFree(ps->p);
     }
@@ -3354,19 +3374,13 @@ int msckf_run_associate(msckf_ctx* c, const msckf_assoc_params* ap, const double
     if (F == 0) return MSCKF_OK;
     if (!matched_uv || !result) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    // inverse of K as the reference forms it for these tests (np.linalg.inv(self.K), MSCKF.py:345)
     const double* K = ap->K;
-    const double det = K[0] * (K[4] * K[8] - K[5] * K[7]) - K[1] * (K[3] * K[8] - K[5] * K[6]) + K[2] * (K[3] * K[7] - K[4] * K[6]);
-    if (det == 0.0) return MSCKF_ERR_ARG;
     AssocArgs a{};
+    if (!assoc_kinv(K, a.Kinv)) return MSCKF_ERR_ARG;
     a.F = F;
     a.view_ptr = ptr<int>(c->dViewPtr); a.obs_uv = ptr<double>(c->dObsUV); a.obs_slot = ptr<int>(c->dObsSlot);
     a.cam_R = ptr<double>(c->dCamR); a.cam_t = ptr<double>(c->dCamT);
     std::memcpy(a.K, K, 72);
-    const double id = 1.0 / det;
-    a.Kinv[0] = (K[4] * K[8] - K[5] * K[7]) * id; a.Kinv[1] = (K[2] * K[7] - K[1] * K[8]) * id; a.Kinv[2] = (K[1] * K[5] - K[2] * K[4]) * id;
-    a.Kinv[3] = (K[5] * K[6] - K[3] * K[8]) * id; a.Kinv[4] = (K[0] * K[8] - K[2] * K[6]) * id; a.Kinv[5] = (K[2] * K[3] - K[0] * K[5]) * id;
-    a.Kinv[6] = (K[3] * K[7] - K[4] * K[6]) * id; a.Kinv[7] = (K[1] * K[6] - K[0] * K[7]) * id; a.Kinv[8] = (K[0] * K[4] - K[1] * K[3]) * id;
     std::memcpy(a.R2, ap->R_cur, 72); std::memcpy(a.t2, ap->t_cur, 24);
     a.thr_epipolar = ap->epipolar_threshold; a.thr_homography = ap->homography_threshold;
     // matched keypoints in sorted feature order; results come back through the same permutation
@@ -3609,6 +3623,21 @@ int msckf_commit_inject(msckf_ctx* c) {
 }
 
 // ---- the track store: views and bases in HBM, batches by track id (k_tracks.h) -----------------------------------
+// the batch of the listed rows (input order) with these counters: msckf_set_features + msckf_set_tracks from the store
+static int tracks_load_rows(msckf_ctx* c, int F, const std::vector<int>& rows, const std::vector<int>& view_ptr,
+                            const int32_t* lost_for, const int32_t* tracked_for) {
+    const int V = c->maxV;
+    std::vector<int> slots(view_ptr[F]);
+    for (int f = 0; f < F; ++f)
+        std::memcpy(slots.data() + view_ptr[f], &c->trk_slots[(size_t)rows[f] * V], (size_t)c->trk_M[rows[f]] * 4);
+    const TrackEmitSrc src{rows.data(), lost_for, tracked_for};
+    const int rc = set_features_impl(c, F, view_ptr.data(), nullptr, slots.data(), nullptr, nullptr, nullptr, &src);
+    if (rc != MSCKF_OK) return rc;
+    c->have_tracks = true;                // the lines and counters went with the batch (msckf_set_tracks' half)
+    c->batch_from_store = F > 0;
+    return MSCKF_OK;
+}
+
 int msckf_tracks_reset(msckf_ctx* c) {
     if (!c) return MSCKF_ERR_ARG;
     tracks_clear(c);
@@ -3622,7 +3651,7 @@ int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const doub
     if (!ids || !uv || !score) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = tracks_ensure(c)) return rc;
-    const int newest = c->N - 1, V = c->maxM;
+    const int newest = c->N - 1, V = c->maxV;
     // every check first: an erroring call leaves the store exactly as it was
     {
         std::unordered_set<int> seen;
@@ -3647,8 +3676,10 @@ int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const doub
             r = c->trk_free.back(); c->trk_free.pop_back();
             c->trk_row_of.emplace(ids[i], r);
             c->trk_id[r] = ids[i]; c->trk_M[r] = 0; c->trk_anchor[r] = newest;
+            c->trk_seq[r] = c->trk_next_seq++;
             fresh = 1;
         } else r = it->second;
+        ++c->trk_tracked[r]; c->trk_lost[r] = 0;                    // an append (MSCKF.py:411-412)
         const int pos = c->trk_M[r]++;
         c->trk_slots[(size_t)r * V + pos] = newest;
         ++c->trk_views;
@@ -3677,8 +3708,7 @@ int msckf_tracks_load(msckf_ctx* c, int32_t F, const int32_t* ids, const int32_t
     if (!c || F < 0 || F > c->maxF) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     if (F > 0 && (!ids || !lost_for || !tracked_for)) return MSCKF_ERR_ARG;
-    const int V = c->maxM;
-    std::vector<int> rows(F), view_ptr(F + 1, 0), slots;
+    std::vector<int> rows(F), view_ptr(F + 1, 0);
     {
         std::unordered_set<int> seen;
         for (int f = 0; f < F; ++f) {
@@ -3688,14 +3718,133 @@ int msckf_tracks_load(msckf_ctx* c, int32_t F, const int32_t* ids, const int32_t
             view_ptr[f + 1] = view_ptr[f] + c->trk_M[rows[f]];
         }
     }
-    slots.resize(view_ptr[F]);
-    for (int f = 0; f < F; ++f)
-        std::memcpy(slots.data() + view_ptr[f], &c->trk_slots[(size_t)rows[f] * V], (size_t)c->trk_M[rows[f]] * 4);
-    const TrackEmitSrc src{rows.data(), lost_for, tracked_for};
-    const int rc = set_features_impl(c, F, view_ptr.data(), nullptr, slots.data(), nullptr, nullptr, nullptr, &src);
-    if (rc != MSCKF_OK) return rc;
-    c->have_tracks = true;                // the lines and counters went with the batch (msckf_set_tracks' half)
-    c->batch_from_store = F > 0;
+    return tracks_load_rows(c, F, rows, view_ptr, lost_for, tracked_for);
+}
+
+// ---- a frame's intake on the store, and what the mirror knows ------------------------------------------
+int msckf_tracks_frame(msckf_ctx* c, const msckf_frame_params* fp, int32_t n, const int32_t* ids, const double* uv,
+                       const double* score, uint8_t* result, int32_t* fail_view) {
+    if (!c || !fp || n < 0) return MSCKF_ERR_ARG;
+    if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
+    if (n > 0 && (!ids || !uv || !score || !result)) return MSCKF_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = tracks_ensure(c)) return rc;
+    const int newest = c->N - 1, V = c->maxV, T = c->maxF;
+    TrackFrameArgs a{};
+    if (!assoc_kinv(fp->K, a.Kinv_test)) return MSCKF_ERR_ARG;
+    // every check first: an erroring call leaves the store and the counters exactly as they were
+    {
+        std::unordered_set<int> seen;
+        size_t fresh = 0;
+        for (int i = 0; i < n; ++i) {
+            if (ids[i] < 0 || !std::isfinite(uv[2 * i]) || !std::isfinite(uv[2 * i + 1])) return MSCKF_ERR_ARG;
+            if (!seen.insert(ids[i]).second) return MSCKF_ERR_DUP_SLOT;
+            const auto it = c->trk_row_of.find(ids[i]);
+            if (it == c->trk_row_of.end()) { ++fresh; continue; }
+            const int r = it->second, M = c->trk_M[r];
+            if (M > 0 && c->trk_slots[(size_t)r * V + M - 1] == newest) return MSCKF_ERR_DUP_SLOT;
+            if (M + 1 > V) return MSCKF_ERR_ARG;
+        }
+        if (fresh > c->trk_free.size()) return MSCKF_ERR_ARG;
+    }
+    std::vector<char> listed(T, 0);
+    if (n > 0) {
+        // the image: n records the kernel reads | n failing views | n result bytes it writes
+        const size_t o_fv = (size_t)n * sizeof(TrackObsRec), o_res = o_fv + (size_t)n * 4;
+        if (int rc = stage_acquire(c, c->trk_frame_stage, o_res + (size_t)n)) return rc;
+        char* img = static_cast<char*>(c->trk_frame_stage.p);
+        TrackObsRec* rec = reinterpret_cast<TrackObsRec*>(img);
+        size_t taken = 0;                 // fresh pairs take the rows the free stack hands out next, in the listed order
+        for (int i = 0; i < n; ++i) {
+            const auto it = c->trk_row_of.find(ids[i]);
+            const bool fresh = it == c->trk_row_of.end();
+            const int r = fresh ? c->trk_free[c->trk_free.size() - 1 - taken++] : it->second;
+            rec[i] = TrackObsRec{r, fresh ? 0 : c->trk_M[r], fresh ? 1 : 0, 0, uv[2 * i], uv[2 * i + 1], score[i]};
+        }
+        a.s = c->trk; a.rec = rec; a.n = n; a.slot = newest;
+        a.cam_R = ptr<double>(c->dCamR); a.cam_t = ptr<double>(c->dCamT);
+        std::memcpy(a.K, fp->K, sizeof(a.K));
+        std::memcpy(a.Kinv, c->Kinv, sizeof(a.Kinv));
+        a.thr_epipolar = fp->epipolar_threshold; a.thr_homography = fp->homography_threshold;
+        a.fail_view = reinterpret_cast<int*>(img + o_fv); a.result = reinterpret_cast<unsigned char*>(img + o_res);
+        hipLaunchKernelGGL(k_track_frame, dim3((n + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));                 // the mirror needs the results: the call blocks
+        for (int i = 0; i < n; ++i) {
+            const TrackObsRec& q = rec[i];
+            const int r = q.row, res = a.result[i];
+            listed[r] = 1;
+            result[i] = (uint8_t)res;
+            if (fail_view) fail_view[i] = a.fail_view[i];
+            if (q.fresh) {
+                c->trk_free.pop_back();
+                c->trk_row_of.emplace(ids[i], r);
+                c->trk_id[r] = ids[i]; c->trk_M[r] = 0; c->trk_anchor[r] = newest;
+                c->trk_seq[r] = c->trk_next_seq++;
+                c->trk_tracked[r] = 0; c->trk_lost[r] = 0;
+            }
+            if (res == 1 || res == 2) { ++c->trk_lost[r]; continue; }               // MSCKF.py:400
+            c->trk_slots[(size_t)r * V + c->trk_M[r]++] = newest;                    // appended (:403-421) or created (:424-436)
+            ++c->trk_views;
+            ++c->trk_tracked[r]; c->trk_lost[r] = 0;                                 // :411-412
+        }
+    }
+    for (int r = 0; r < T; ++r) if (c->trk_id[r] >= 0 && !listed[r]) ++c->trk_lost[r];   // not matched in this frame (:438)
+    return MSCKF_OK;
+}
+
+int msckf_tracks_load_where(msckf_ctx* c, int32_t n_slots, const int32_t* slots, int32_t* F_out, int32_t* ids_out, int32_t cap) {
+    if (!c || n_slots < 0 || cap < 0 || !F_out || (n_slots > 0 && !slots) || (cap > 0 && !ids_out)) return MSCKF_ERR_ARG;
+    if (!c->have_state) return MSCKF_ERR_STATE;
+    std::vector<char> want(std::max(c->N, 1), n_slots == 0);
+    for (int i = 0; i < n_slots; ++i) {
+        if (slots[i] < 0 || slots[i] >= c->N) return MSCKF_ERR_ARG;
+        want[slots[i]] = 1;
+    }
+    const int V = c->maxV;
+    std::vector<std::pair<long long, int>> cand;                    // (creation number, row): the reference's dict order
+    if (c->trk_ready)
+        for (int r = 0; r < c->maxF; ++r) {
+            if (c->trk_id[r] < 0) continue;
+            bool hit = n_slots == 0;
+            for (int v = 0; !hit && v < c->trk_M[r]; ++v) hit = want[c->trk_slots[(size_t)r * V + v]];
+            if (hit) cand.emplace_back(c->trk_seq[r], r);
+        }
+    std::sort(cand.begin(), cand.end());
+    const int F = (int)cand.size();
+    if (F > cap) return MSCKF_ERR_ARG;
+    std::vector<int> rows(F), view_ptr(F + 1, 0), lost(F), tracked(F);
+    for (int f = 0; f < F; ++f) {
+        const int r = cand[f].second;
+        rows[f] = r; lost[f] = c->trk_lost[r]; tracked[f] = c->trk_tracked[r];
+        view_ptr[f + 1] = view_ptr[f] + c->trk_M[r];
+    }
+    if (int rc = tracks_load_rows(c, F, rows, view_ptr, lost.data(), tracked.data())) return rc;
+    for (int f = 0; f < F; ++f) ids_out[f] = c->trk_id[rows[f]];
+    *F_out = F;
+    return MSCKF_OK;
+}
+
+int msckf_tracks_counters(msckf_ctx* c, int32_t n, const int32_t* ids, int32_t* lost_for, int32_t* tracked_for) {
+    if (!c || n < 0 || (n > 0 && !ids)) return MSCKF_ERR_ARG;
+    for (int i = 0; i < n; ++i) if (!c->trk_row_of.count(ids[i])) return MSCKF_ERR_ARG;
+    for (int i = 0; i < n; ++i) {
+        const int r = c->trk_row_of[ids[i]];
+        if (lost_for) lost_for[i] = c->trk_lost[r];
+        if (tracked_for) tracked_for[i] = c->trk_tracked[r];
+    }
+    return MSCKF_OK;
+}
+
+int msckf_tracks_clone_views(msckf_ctx* c, int32_t* views) {
+    if (!c || (c->N > 0 && !views)) return MSCKF_ERR_ARG;
+    if (!c->have_state) return MSCKF_ERR_STATE;
+    for (int s = 0; s < c->N; ++s) views[s] = 0;
+    if (!c->trk_ready) return MSCKF_OK;
+    const int V = c->maxV;
+    for (int r = 0; r < c->maxF; ++r)
+        if (c->trk_id[r] >= 0)
+            for (int v = 0; v < c->trk_M[r]; ++v) ++views[c->trk_slots[(size_t)r * V + v]];
     return MSCKF_OK;
 }
 
@@ -3705,7 +3854,7 @@ int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, d
     const auto it = c->trk_row_of.find(id);
     if (it == c->trk_row_of.end()) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t r = it->second, V = c->maxM, N = c->N;
+    const size_t r = it->second, V = c->maxV, N = c->N;
     const int M = c->trk_M[r];
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const TrackStore& s = c->trk;

@@ -374,6 +374,49 @@ int msckf_tracks_counters(msckf_ctx* ctx, int32_t n, const int32_t* ids, int32_t
  * clone of get_cameras_without_features (:781-790). */
 int msckf_tracks_clone_views(msckf_ctx* ctx, int32_t* views /*N*/);
 
+/* ---- frame intake from descriptors: match on the device against the store ---- *
+ * A frame travels as (keypoints, descriptors, scores); the store answers with track ids and result codes.  Behind every
+ * view the store then keeps its descriptor ([T][V][64] fp32, XFeat's dtype; desc_dim D in 1..64, rows zero-padded), and
+ * per track one match row ([T][64] fp32): the reference's last_camera_measurement table (MSCKF.py:436-444).  The row is a
+ * SNAPSHOT, recomputed only at the end of an intake as fp32(sum_v fp64(d_v) conf_v / sum_v conf_v) over the track's views
+ * in view order (:439); msckf_remove_clones compacts the per-view descriptors (:766) and leaves the row stale until the
+ * next intake, as the reference does; on an empty store (:291-311) the row is the raw descriptor, bit for bit (:311).
+ * Both arrays are allocated by the first msckf_tracks_match_frame.  The store's D is set by the first successful intake
+ * and cleared by msckf_tracks_reset / msckf_set_state.
+ * The matching rule (XFeat.match, mutual nearest neighbour): A = the rows of the live tracks in the order the tracks were
+ * created, B = the frame; S = A B^T in fp32 (v_mfma_f32_16x16x4_f32; no normalisation), m12[i] = argmax_j S[i][j],
+ * m21[j] = argmax_i S[i][j], ties to the lowest index (the earliest-created track); (i, m12[i]) is a match iff
+ * m21[m12[i]] == i and S[i][m12[i]] > min_cosine_similarity (strict; compared in double).
+ * Errors, nothing changed: MSCKF_ERR_ARG for D outside 1..64 or different from the store's D, a non-finite descriptor, a
+ * negative first_new_id or a new id that collides with a live one, more creations than free rows; MSCKF_ERR_STATE when
+ * N = 0 or the store holds a track with a view that has no descriptor (tracks fed by msckf_tracks_observe or
+ * msckf_tracks_frame are such tracks); otherwise those of msckf_tracks_frame. */
+/* Match only, the store is untouched: track_id_out[n] = the matched track's id or -1, sim_out[n] (nullable) = the pair's
+ * similarity, 0 where unmatched.  Blocking. */
+int msckf_tracks_match(msckf_ctx* ctx, double min_cosine_similarity, int32_t desc_dim, int32_t n, const float* desc /*n*D*/,
+                       int32_t* track_id_out /*n*/, float* sim_out /*n, nullable*/);
+typedef struct msckf_match_params {
+    double K[9];                    /* as msckf_frame_params                                            */
+    double epipolar_threshold;
+    double homography_threshold;
+    double min_cosine_similarity;   /* MSCKFParameters.min_cosine_similarity                            */
+    int32_t desc_dim;               /* D                                                                */
+    int32_t first_new_id;           /* created tracks get first_new_id, +1, ... in ascending keypoint order */
+} msckf_match_params;
+/* The else-branch of MSCKF.add_camera_measurements (:315-444): match; the matched pairs go through msckf_tracks_frame's
+ * path (codes 0 / 1 / 2, same stored bits, same counters); every unmatched keypoint creates a track (code 4), ids in
+ * ascending keypoint order (np.setdiff1d, FeatureExtractor.py:72); lost_for += 1 for every unmatched track (:438); all
+ * rows are recomputed.  ids_out[n]: the track each keypoint went to or created.  Returns 1 with NOTHING changed when
+ * n == 0 (:286) or no pair matched (:320: no new tracks, no counters, no rows).  On an empty store everything is created
+ * and the rows are raw.  Blocking. */
+int msckf_tracks_match_frame(msckf_ctx* ctx, const msckf_match_params* params, int32_t n, const float* desc /*n*D*/,
+                             const double* uv /*2n*/, const double* score /*n*/, int32_t* ids_out /*n*/, uint8_t* result /*n*/,
+                             int32_t* fail_view /*n, nullable*/, float* sim_out /*n, nullable*/);
+/* One track's descriptors as they stand on the device (blocking; any output may be NULL): its match row, row[D], its M
+ * views and their descriptors, views[M*D] (room for max_track * D).  MSCKF_ERR_ARG: unknown id; MSCKF_ERR_STATE: the
+ * track has a view without a descriptor. */
+int msckf_tracks_descriptor(msckf_ctx* ctx, int32_t id, float* row /*D*/, int32_t* M, float* views /*M*D*/);
+
 /* ---- feature-sharded path (one context per GPU / rank) ------------------ *
  * Each rank holds a shard of the features and the full state.  It runs K1-K5
  * locally and exports its compressed block [R | Q^T r]: (6N) x (6N+1) doubles,

@@ -39,6 +39,7 @@ SYMBOLS = [
     "msckf_tracks_reset", "msckf_tracks_observe", "msckf_tracks_remove", "msckf_tracks_load", "msckf_tracks_get",
     "msckf_tracks_count", "msckf_tracks_dropped",
     "msckf_tracks_frame", "msckf_tracks_load_where", "msckf_tracks_counters", "msckf_tracks_clone_views",
+    "msckf_tracks_match", "msckf_tracks_match_frame", "msckf_tracks_descriptor",
 ]
 
 
@@ -68,6 +69,15 @@ class FrameParamsC(C.Structure):
     _fields_ = [("K", C.c_double * 9), ("epipolar_threshold", C.c_double), ("homography_threshold", C.c_double)]
 
 
+class MatchParamsC(C.Structure):
+    """msckf_match_params: msckf_frame_params + the matcher's threshold, the descriptor dimension, the first new id."""
+    _fields_ = [("K", C.c_double * 9), ("epipolar_threshold", C.c_double), ("homography_threshold", C.c_double),
+                ("min_cosine_similarity", C.c_double), ("desc_dim", C.c_int32), ("first_new_id", C.c_int32)]
+
+
+DESC_DIM = 64           # floats a stored descriptor row holds: desc_dim is 1..64
+
+
 class SelectParamsC(C.Structure):
     _fields_ = [("min_frames_lost", C.c_int32), ("min_frames_tracked", C.c_int32), ("use_parallax", C.c_int32),
                 ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32),
@@ -92,6 +102,7 @@ _lib = None
 _dp = C.c_void_p
 _ip = C.c_void_p
 _up = C.c_void_p
+_fp = C.c_void_p
 
 
 def load():
@@ -231,7 +242,11 @@ def load():
     lib.msckf_tracks_load_where.argtypes = [vp, C.c_int32, _ip, _ip, _ip, C.c_int32]
     lib.msckf_tracks_counters.argtypes = [vp, C.c_int32, _ip, _ip, _ip]
     lib.msckf_tracks_clone_views.argtypes = [vp, _ip]
-    for name in ("reset", "observe", "remove", "load", "get", "count", "dropped", "frame", "load_where", "counters", "clone_views"):
+    lib.msckf_tracks_match.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, _fp, _ip, _fp]
+    lib.msckf_tracks_match_frame.argtypes = [vp, C.POINTER(MatchParamsC), C.c_int32, _fp, _dp, _dp, _ip, _up, _ip, _fp]
+    lib.msckf_tracks_descriptor.argtypes = [vp, C.c_int32, _fp, _ip, _fp]
+    for name in ("reset", "observe", "remove", "load", "get", "count", "dropped", "frame", "load_where", "counters", "clone_views",
+                 "match", "match_frame", "descriptor"):
         getattr(lib, "msckf_tracks_" + name).restype = C.c_int
     lib.msckf_debug_split.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.msckf_debug_split.restype = C.c_int
@@ -245,6 +260,10 @@ def load():
 
 def f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
 
 
 def i32(a):

@@ -111,6 +111,7 @@ class UpdateEngine:
         self.max_clones, self.max_features, self.max_track = max_clones, max_features, max_track
         self._N = 0
         self._F = 0
+        self._desc_dim = 0      # D of the last tracks_match_frame that went in (track_descriptor trims to it)
 
     # -- lifetime -----------------------------------------------------------
     def close(self):
@@ -463,6 +464,72 @@ class UpdateEngine:
         self._check(self._lib.msckf_tracks_frame(self._h, C.byref(fp), n, _ffi.iptr(i), _ffi.dptr(u), _ffi.dptr(s),
                                                  _ffi.uptr(res), _ffi.iptr(fv)), allow_noop=False)
         return res[:n].copy(), fv[:n].copy()
+
+    # -- frame intake from descriptors: the match runs on the device against the store's rows --------
+    @staticmethod
+    def _desc(descriptors):
+        """(n, D) descriptors as fp32 (XFeat's dtype): fp64 input, such as the data set's CSV descriptors, is rounded here."""
+        d = _ffi.f32(descriptors)
+        if d.ndim != 2:
+            raise ValueError("descriptors are (n, D)")
+        return d
+
+    def tracks_match(self, descriptors, min_cosine_similarity: float = 0.82):
+        """The mutual-nearest-neighbour match of a frame's descriptors against the store's rows (reference
+        `FeatureExtractor.match`, `FeatureExtractor.py:62-84`); the store is untouched.  Returns (track id (n,) int32, -1
+        where unmatched; similarity (n,) fp32, 0 where unmatched).  Blocking."""
+        d = self._desc(descriptors)
+        n, D = d.shape
+        ids, sim = np.full(max(n, 1), -1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.float32)
+        self._check(self._lib.msckf_tracks_match(self._h, float(min_cosine_similarity), int(D), int(n), _ffi.dptr(d),
+                                                 _ffi.iptr(ids), _ffi.dptr(sim)), allow_noop=False)
+        return ids[:n].copy(), sim[:n].copy()
+
+    def tracks_match_frame(self, keypoints, descriptors, scores, K, first_new_id: int, min_cosine_similarity: float = 0.82,
+                           epipolar_threshold: float = 5.0, homography_threshold: float = 5.0):
+        """A frame as (keypoints (n, 2), descriptors (n, D), scores (n,)) on the store: the else-branch of the reference's
+        `add_camera_measurements` (`MSCKF.py:315-444`).  Matched pairs go through `tracks_frame`'s tests, every unmatched
+        keypoint creates a track with ids `first_new_id, +1, ...` in ascending keypoint order, the counters follow and all
+        match rows are recomputed.  Returns None when the reference skips the frame (no keypoint, `:286`; no pair matched,
+        `:320`: nothing changed), else (ids (n,) int32, result (n,) uint8: 0 appended, 1 / 2 epipolar / homography failure,
+        4 created; fail_view (n,) int32; similarity (n,) fp32).  Blocking."""
+        d = self._desc(descriptors)
+        n, D = d.shape
+        u, s = _ffi.f64(keypoints).reshape(-1), _ffi.f64(scores).reshape(-1)
+        if u.size != 2 * n or s.size != n:
+            raise ValueError("keypoints are (n, 2), scores (n,)")
+        mp = _ffi.MatchParamsC()
+        mp.K = (C.c_double * 9)(*np.asarray(K, dtype=np.float64).reshape(9))
+        mp.epipolar_threshold, mp.homography_threshold = float(epipolar_threshold), float(homography_threshold)
+        mp.min_cosine_similarity, mp.desc_dim, mp.first_new_id = float(min_cosine_similarity), int(D), int(first_new_id)
+        ids, fv = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        res, sim = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.float32)
+        rc = self._check(self._lib.msckf_tracks_match_frame(self._h, C.byref(mp), int(n), _ffi.dptr(d), _ffi.dptr(u), _ffi.dptr(s),
+                                                            _ffi.iptr(ids), _ffi.uptr(res), _ffi.iptr(fv), _ffi.dptr(sim)))
+        if rc == _ffi.NOOP:
+            return None
+        self._desc_dim = int(D)
+        return ids[:n].copy(), res[:n].copy(), fv[:n].copy(), sim[:n].copy()
+
+    def frame_from_extracted(self, keypoints, descriptors, scores, K, first_new_id: int, **kw):
+        """`tracks_match_frame` behind the reference's score floor (`MSCKF.py:281-284`): keypoints whose score is below
+        half the frame's mean score (`np.mean`) are dropped first.  Returns (kept, out): the indices of the keypoints that
+        went in and what `tracks_match_frame` returned for them (None: the frame was skipped)."""
+        scores = np.asarray(scores)
+        kept = np.nonzero(scores >= 0.5 * np.mean(scores))[0] if scores.size else np.zeros(0, dtype=np.int64)
+        d = np.asarray(descriptors)
+        d = d[kept] if d.ndim == 2 else d.reshape(0, 1)
+        return kept, self.tracks_match_frame(np.asarray(keypoints).reshape(-1, 2)[kept], d, scores[kept], K, first_new_id, **kw)
+
+    def track_descriptor(self, track_id: int):
+        """(match row (D,), per-view descriptors (M, D)) of one track as they stand on the device, fp32.  Blocking."""
+        row = np.zeros(_ffi.DESC_DIM, dtype=np.float32)
+        views = np.zeros(_ffi.MAX_TRACK_ROW * _ffi.DESC_DIM, dtype=np.float32)
+        M = C.c_int32(0)
+        self._check(self._lib.msckf_tracks_descriptor(self._h, int(track_id), _ffi.dptr(row), C.addressof(M), _ffi.dptr(views)),
+                    allow_noop=False)
+        D = self._desc_dim
+        return row[:D].copy(), views[:int(M.value) * D].reshape(int(M.value), D).copy()
 
     def load_tracks_where(self, slots=None) -> np.ndarray:
         """`load_tracks` with the stored counters for every track (`slots` None or empty: `process_features`' candidates)

@@ -38,6 +38,7 @@
 #include "k_nominal.h"
 #include "k_assoc.h"
 #include "k_tracks.h"
+#include "k_match.h"
 #include "run_outcome.h"
 
 using namespace msckf;
@@ -497,6 +498,14 @@ struct msckf_ctx {
     long long trk_views = 0;
     bool batch_from_store = false;        // the current batch came through msckf_tracks_load: msckf_run_select writes refreshed points back
     PinStage trk_obs_stage, trk_load_stage, trk_frame_stage;
+    // descriptors behind the store (k_match.h): per-view rows and one match row per track, allocated by the first call that
+    // brings descriptors.  trk_hasdesc: every view of the row came with one (msckf_tracks_match_frame made them all).
+    Buf dDescViews, dDescRow, dMatch;
+    DescStore desc{};
+    bool desc_ready = false;
+    int desc_D = 0;                       // the store's descriptor dimension; 0: not set yet
+    std::vector<char> trk_hasdesc;
+    PinStage trk_match_stage, trk_desc_stage;
     long fetched_serial = -1;             // the run whose return code msckf_get_result derived last ...
     int fetched_rc = 0;                   // ... and that code: msckf_commit_covariance need not read the gate results again
 };
@@ -2128,8 +2137,10 @@ void tracks_clear(msckf_ctx* c) {
     c->trk_dropped.clear();
     c->trk_views = 0;
     c->batch_from_store = false;
+    c->desc_D = 0;
     if (!c->trk_ready) return;
     const int T = c->maxF;
+    std::fill(c->trk_hasdesc.begin(), c->trk_hasdesc.end(), 0);
     std::fill(c->trk_id.begin(), c->trk_id.end(), -1);
     std::fill(c->trk_M.begin(), c->trk_M.end(), 0);
     std::fill(c->trk_lost.begin(), c->trk_lost.end(), 0);
@@ -2156,6 +2167,7 @@ int tracks_ensure(msckf_ctx* c) {
     s.count = reinterpret_cast<int*>(b + o_count); s.V = (int)V;
     c->trk_id.assign(T, -1); c->trk_M.assign(T, 0); c->trk_anchor.assign(T, -1); c->trk_slots.assign(TV, 0);
     c->trk_lost.assign(T, 0); c->trk_tracked.assign(T, 0); c->trk_seq.assign(T, 0);
+    c->trk_hasdesc.assign(T, 0);
     c->trk_ready = true;
     tracks_clear(c);
     return MSCKF_OK;
@@ -2166,6 +2178,7 @@ inline void tracks_free_row(msckf_ctx* c, int row) {
     c->trk_views -= c->trk_M[row];
     c->trk_id[row] = -1; c->trk_M[row] = 0;
     c->trk_lost[row] = c->trk_tracked[row] = 0;                     // the counters die with the track
+    c->trk_hasdesc[row] = 0;
     c->trk_free.push_back(row);
     c->batch_from_store = false;          // (the row may be handed out again: a loaded batch no longer writes refreshed points back)
 }
@@ -2219,6 +2232,10 @@ int tracks_drop_clones(msckf_ctx* c, const std::vector<char>& drop) {
     for (int r = 0; r < c->maxF; ++r) if (c->trk_id[r] >= 0) rows.push_back(r);
     a.s = c->trk; a.rows = ptr<int>(c->dTrkRows); a.n = (int)rows.size(); a.cam_t = ptr<double>(c->dCamT);
     HIPCHK(c, hipMemcpyAsync(c->dTrkRows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (c->desc_ready) {                  // the descriptor views first: k_desc_drop reads the slots k_track_drop renumbers
+        hipLaunchKernelGGL(k_desc_drop, dim3(a.n), dim3(64), 0, c->stream, c->desc, a);
+        HIPCHK(c, hipGetLastError());
+    }
     hipLaunchKernelGGL(k_track_drop, dim3((a.n + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));                     // (`rows` is pageable memory; the call is a blocking one anyway)
@@ -2459,7 +2476,8 @@ void msckf_destroy(msckf_ctx* c) {
                   &c->dLineBase, &c->dLineDir, &c->dLineConf, &c->dLostFor, &c->dTrackedFor, &c->dSelFlags, &c->dWorld,
                   &c->dFlush, &c->dFlushOff, &c->dFeatInfo, &c->dCommBuf, &c->dAssocUV, &c->dAssocRes,
                   &c->dGsEx, &c->dGsFlag, &c->dGsProg, &c->dMProg, &c->dMFlush, &c->dRootFlush, &c->dXRootFlush,
-                  &c->dSplit, &c->dRem, &c->dNom, &c->dTrk, &c->dTrkRows, &c->dTrkRowSorted};
+                  &c->dSplit, &c->dRem, &c->dNom, &c->dTrk, &c->dTrkRows, &c->dTrkRowSorted,
+                  &c->dDescViews, &c->dDescRow, &c->dMatch};
     for (Buf* b : all) if (b->p && !b->view) (void)hipFree(b->p);
     for (Buf* b : {&c->dPoseArena, &c->dFeatArena, &c->dRawArena, &c->dResArena, &c->dGateArena, &c->dPlanArena}) if (b->p) (void)hipFree(b->p);
     for (void* h : {c->hPose, c->hFeat, c->hRes, c->hGate, c->hP}) if (h) (void)hipHostFree(h);
@@ -2473,7 +2491,7 @@ void msckf_destroy(msckf_ctx* c) {
     if (c->hPlan) (void)hipHostFree(c->hPlan);
     if (c->ev_state) (void)hipEventDestroy(c->ev_state);
     if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
-    for (PinStage* ps : {&c->trk_obs_stage, &c->trk_load_stage, &c->trk_frame_stage}) {
+    for (PinStage* ps : {&c->trk_obs_stage, &c->trk_load_stage, &c->trk_frame_stage, &c->trk_match_stage, &c->trk_desc_stage}) {
         if (ps->ev) (void)hipEventDestroy(ps->ev);
         if (ps->p) (void)hipHostFree(ps->p);
     }
@@ -3680,6 +3698,7 @@ int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const doub
             fresh = 1;
         } else r = it->second;
         ++c->trk_tracked[r]; c->trk_lost[r] = 0;                    // an append (MSCKF.py:411-412)
+        c->trk_hasdesc[r] = 0;                                      // (a view without a descriptor)
         const int pos = c->trk_M[r]++;
         c->trk_slots[(size_t)r * V + pos] = newest;
         ++c->trk_views;
@@ -3722,8 +3741,9 @@ int msckf_tracks_load(msckf_ctx* c, int32_t F, const int32_t* ids, const int32_t
 }
 
 // ---- a frame's intake on the store, and what the mirror knows ------------------------------------------
-int msckf_tracks_frame(msckf_ctx* c, const msckf_frame_params* fp, int32_t n, const int32_t* ids, const double* uv,
-                       const double* score, uint8_t* result, int32_t* fail_view) {
+// with_desc: the caller stores a descriptor for every view this call appends or creates (msckf_tracks_match_frame)
+static int tracks_frame_impl(msckf_ctx* c, const msckf_frame_params* fp, int32_t n, const int32_t* ids, const double* uv,
+                             const double* score, uint8_t* result, int32_t* fail_view, bool with_desc) {
     if (!c || !fp || n < 0) return MSCKF_ERR_ARG;
     if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
     if (n > 0 && (!ids || !uv || !score || !result)) return MSCKF_ERR_ARG;
@@ -3782,14 +3802,184 @@ int msckf_tracks_frame(msckf_ctx* c, const msckf_frame_params* fp, int32_t n, co
                 c->trk_id[r] = ids[i]; c->trk_M[r] = 0; c->trk_anchor[r] = newest;
                 c->trk_seq[r] = c->trk_next_seq++;
                 c->trk_tracked[r] = 0; c->trk_lost[r] = 0;
+                c->trk_hasdesc[r] = with_desc;
             }
             if (res == 1 || res == 2) { ++c->trk_lost[r]; continue; }               // MSCKF.py:400
+            if (!with_desc) c->trk_hasdesc[r] = 0;
             c->trk_slots[(size_t)r * V + c->trk_M[r]++] = newest;                    // appended (:403-421) or created (:424-436)
             ++c->trk_views;
             ++c->trk_tracked[r]; c->trk_lost[r] = 0;                                 // :411-412
         }
     }
     for (int r = 0; r < T; ++r) if (c->trk_id[r] >= 0 && !listed[r]) ++c->trk_lost[r];   // not matched in this frame (:438)
+    return MSCKF_OK;
+}
+
+int msckf_tracks_frame(msckf_ctx* c, const msckf_frame_params* fp, int32_t n, const int32_t* ids, const double* uv,
+                       const double* score, uint8_t* result, int32_t* fail_view) {
+    return tracks_frame_impl(c, fp, n, ids, uv, score, result, fail_view, false);
+}
+
+// ---- frame intake from descriptors: match on the device against the store (k_match.h) -------------------
+// the two descriptor arrays, on the first call that brings descriptors
+static int desc_ensure(msckf_ctx* c) {
+    if (c->desc_ready) return MSCKF_OK;
+    if (int rc = tracks_ensure(c)) return rc;
+    const size_t T = c->maxF, V = c->maxV;
+    if (int rc = ensure(c, c->dDescViews, T * V * DESC_DIM * 4, true)) return rc;
+    if (int rc = ensure(c, c->dDescRow, T * DESC_DIM * 4, true)) return rc;
+    c->desc.views = ptr<float>(c->dDescViews); c->desc.row = ptr<float>(c->dDescRow); c->desc.V = (int)V;
+    c->desc_ready = true;
+    return MSCKF_OK;
+}
+
+// the checks every descriptor call makes; the live rows in the order their tracks were created
+static int match_check(msckf_ctx* c, int32_t D, int32_t n, const float* desc, std::vector<int>& rows) {
+    if (D < 1 || D > DESC_DIM || (c->desc_D != 0 && D != c->desc_D)) return MSCKF_ERR_ARG;
+    if (n > 0 && !desc) return MSCKF_ERR_ARG;
+    for (size_t i = 0; i < (size_t)n * D; ++i) if (!std::isfinite(desc[i])) return MSCKF_ERR_ARG;
+    rows.clear();
+    if (!c->trk_ready) return MSCKF_OK;
+    std::vector<std::pair<long long, int>> live;
+    for (int r = 0; r < c->maxF; ++r) {
+        if (c->trk_id[r] < 0) continue;
+        if (!c->trk_hasdesc[r]) { c->last_error = "track store: a track holds a view without a descriptor"; return MSCKF_ERR_STATE; }
+        live.emplace_back(c->trk_seq[r], r);
+    }
+    std::sort(live.begin(), live.end());
+    for (const auto& e : live) rows.push_back(e.second);
+    return MSCKF_OK;
+}
+
+// The frame goes up (zero-padded rows of 64) and, when the table has rows, is matched against it: pair[t] = the keypoint
+// table element t pairs with or -1, sim[t] = its best similarity, t in creation order.  Blocks.
+static int match_run(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, const std::vector<int>& rows,
+                     std::vector<int>& pair, std::vector<float>& sim) {
+    const size_t T = rows.size(), nf = (size_t)n * DESC_DIM;
+    // pinned image: frame | rows | pair | sim;  device: frame | rows | m12 | sim12 | m21
+    const size_t o_rows = nf * 4, o_pair = o_rows + T * 4, o_sim = o_pair + T * 4;
+    if (int rc = stage_acquire(c, c->trk_match_stage, o_sim + T * 4)) return rc;
+    if (int rc = ensure(c, c->dMatch, o_rows + 3 * T * 4 + (size_t)n * 4)) return rc;
+    char* img = static_cast<char*>(c->trk_match_stage.p);
+    float* hf = reinterpret_cast<float*>(img);
+    std::memset(hf, 0, nf * 4);
+    for (int i = 0; i < n; ++i) std::memcpy(hf + (size_t)i * DESC_DIM, desc + (size_t)i * D, (size_t)D * 4);
+    if (T) std::memcpy(img + o_rows, rows.data(), T * 4);
+    char* dev = static_cast<char*>(c->dMatch.p);
+    HIPCHK(c, hipMemcpyAsync(dev, img, o_pair, hipMemcpyHostToDevice, c->stream));
+    if (T) {
+        const float* dframe = reinterpret_cast<const float*>(dev);
+        const int* drows = reinterpret_cast<const int*>(dev + o_rows);
+        int* m12 = reinterpret_cast<int*>(dev + o_rows + T * 4);
+        float* sim12 = reinterpret_cast<float*>(dev + o_rows + 2 * T * 4);
+        int* m21 = reinterpret_cast<int*>(dev + o_rows + 3 * T * 4);
+        MatchArgmaxArgs a{c->desc.row, drows, (int)T, dframe, nullptr, n, m12, sim12};
+        hipLaunchKernelGGL(k_match_argmax, dim3((a.nx + 15) / 16), dim3(64), 0, c->stream, a);
+        MatchArgmaxArgs b{dframe, nullptr, n, c->desc.row, drows, (int)T, m21, nullptr};
+        hipLaunchKernelGGL(k_match_argmax, dim3((b.nx + 15) / 16), dim3(64), 0, c->stream, b);
+        hipLaunchKernelGGL(k_match_resolve, dim3(((int)T + 255) / 256), dim3(256), 0, c->stream, (int)T, (const int*)m12,
+                           (const float*)sim12, (const int*)m21, min_cos, reinterpret_cast<int*>(img + o_pair),
+                           reinterpret_cast<float*>(img + o_sim));
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    pair.assign(reinterpret_cast<int*>(img + o_pair), reinterpret_cast<int*>(img + o_pair) + T);
+    sim.assign(reinterpret_cast<float*>(img + o_sim), reinterpret_cast<float*>(img + o_sim) + T);
+    return MSCKF_OK;
+}
+
+int msckf_tracks_match(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, int32_t* track_id_out, float* sim_out) {
+    if (!c || n < 0 || (n > 0 && !track_id_out)) return MSCKF_ERR_ARG;
+    if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
+    std::vector<int> rows, pair;
+    std::vector<float> sim;
+    if (int rc = match_check(c, D, n, desc, rows)) return rc;
+    for (int j = 0; j < n; ++j) { track_id_out[j] = -1; if (sim_out) sim_out[j] = 0.f; }
+    if (n == 0 || rows.empty()) return MSCKF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = match_run(c, min_cos, D, n, desc, rows, pair, sim)) return rc;
+    for (size_t t = 0; t < rows.size(); ++t)
+        if (pair[t] >= 0) { track_id_out[pair[t]] = c->trk_id[rows[t]]; if (sim_out) sim_out[pair[t]] = sim[t]; }
+    return MSCKF_OK;
+}
+
+int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t n, const float* desc, const double* uv,
+                             const double* score, int32_t* ids_out, uint8_t* result, int32_t* fail_view, float* sim_out) {
+    if (!c || !mp || n < 0) return MSCKF_ERR_ARG;
+    if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
+    if (n == 0) return MSCKF_NOOP;                                   // MSCKF.py:286
+    if (!desc || !uv || !score || !ids_out || !result || mp->first_new_id < 0) return MSCKF_ERR_ARG;
+    const int D = mp->desc_dim;
+    std::vector<int> rows, pair;
+    std::vector<float> sim;
+    if (int rc = match_check(c, D, n, desc, rows)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = desc_ensure(c)) return rc;
+    const bool empty = rows.empty();                                 // :291-311: everything is created, the rows are raw
+    if (int rc = match_run(c, mp->min_cosine_similarity, D, n, desc, rows, pair, sim)) return rc;
+    std::vector<int32_t> ids(n, -1);
+    std::vector<float> ksim(n, 0.f);
+    int matched = 0;
+    for (size_t t = 0; t < rows.size(); ++t)
+        if (pair[t] >= 0) { ids[pair[t]] = c->trk_id[rows[t]]; ksim[pair[t]] = sim[t]; ++matched; }
+    if (!empty && matched == 0) return MSCKF_NOOP;                   // :320: the frame is skipped as a whole
+    {
+        // ids in ascending keypoint order (np.setdiff1d, FeatureExtractor.py:72); they may not reach past int32 or hit a live id
+        long long next = mp->first_new_id;
+        for (int j = 0; j < n; ++j) {
+            if (ids[j] >= 0) continue;
+            if (next > 0x7fffffffLL || c->trk_row_of.count((int)next)) return MSCKF_ERR_ARG;
+            ids[j] = (int32_t)next++;
+        }
+    }
+    msckf_frame_params fp{};
+    std::memcpy(fp.K, mp->K, sizeof(fp.K));
+    fp.epipolar_threshold = mp->epipolar_threshold; fp.homography_threshold = mp->homography_threshold;
+    std::vector<int32_t> fv(n);
+    if (int rc = tracks_frame_impl(c, &fp, n, ids.data(), uv, score, result, fv.data(), true)) return rc;
+    // the descriptors of the views that went in, then every row anew (:436-441)
+    std::vector<int> all;
+    for (int r = 0; r < c->maxF; ++r) if (c->trk_id[r] >= 0) all.push_back(r);
+    const size_t o_all = (size_t)n * sizeof(DescRec);
+    if (int rc = stage_acquire(c, c->trk_desc_stage, o_all + all.size() * 4)) return rc;
+    char* img = static_cast<char*>(c->trk_desc_stage.p);
+    DescRec* rec = reinterpret_cast<DescRec*>(img);
+    int nrec = 0;
+    for (int j = 0; j < n; ++j) {
+        if (result[j] != 0 && result[j] != 4) continue;
+        const int r = c->trk_row_of[ids[j]];
+        rec[nrec++] = DescRec{r, c->trk_M[r] - 1, j, 0};
+    }
+    std::memcpy(img + o_all, all.data(), all.size() * 4);
+    if (nrec) hipLaunchKernelGGL(k_desc_store, dim3(nrec), dim3(64), 0, c->stream, c->desc, (const DescRec*)rec, (const float*)ptr<float>(c->dMatch));
+    hipLaunchKernelGGL(k_desc_average, dim3((int)all.size()), dim3(64), 0, c->stream, c->desc, c->trk,
+                       reinterpret_cast<const int*>(img + o_all), empty ? 1 : 0);
+    HIPCHK(c, hipGetLastError());
+    c->main_busy = true;
+    c->desc_D = D;
+    for (int j = 0; j < n; ++j) {
+        ids_out[j] = ids[j];
+        if (fail_view) fail_view[j] = fv[j];
+        if (sim_out) sim_out[j] = ksim[j];
+    }
+    return stage_release(c, c->trk_desc_stage);
+}
+
+int msckf_tracks_descriptor(msckf_ctx* c, int32_t id, float* row, int32_t* M_out, float* views) {
+    if (!c) return MSCKF_ERR_ARG;
+    const auto it = c->trk_row_of.find(id);
+    if (it == c->trk_row_of.end()) return MSCKF_ERR_ARG;
+    const size_t r = it->second, V = c->maxV;
+    if (!c->desc_ready || !c->trk_hasdesc[r]) return MSCKF_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int M = c->trk_M[r], D = c->desc_D;
+    std::vector<float> hrow(DESC_DIM), hv((size_t)std::max(M, 1) * DESC_DIM);
+    HIPCHK(c, hipMemcpy(hrow.data(), c->desc.row + r * DESC_DIM, DESC_DIM * 4, hipMemcpyDeviceToHost));
+    if (M) HIPCHK(c, hipMemcpy(hv.data(), c->desc.views + r * V * DESC_DIM, (size_t)M * DESC_DIM * 4, hipMemcpyDeviceToHost));
+    if (row) std::memcpy(row, hrow.data(), (size_t)D * 4);
+    if (views) for (int v = 0; v < M; ++v) std::memcpy(views + (size_t)v * D, &hv[(size_t)v * DESC_DIM], (size_t)D * 4);
+    if (M_out) *M_out = M;
     return MSCKF_OK;
 }
 

@@ -1,0 +1,266 @@
+"""The NumPy model of `dtype = f32` (tests/f32_model.py) on the CPU: what makes its budget fit to hold the engine to.
+
+  1. Without rounding the model is the oracle: the sequential block form at fp64 rounding level on every update golden and on
+     windows of 1 - 82 clones.
+  2. The budget is a stable statistic: the maximum over samples 1 - 16 against the maximum over samples 17 - 32.
+  3. The cap does not bind: MARGIN * budget is below the mode's flat 1e-4 / 1e-5 for every case tests/test_gpu_f32.py runs.
+     This is a condition on the INPUTS, decided here: a case's seed is the first from its base that passes (test_gpu_f32.case_seed;
+     SEED_SKIPS there lists the cases that did not take the base itself).
+  4. The budget can see what the flat tolerance cannot: three defects injected into the model's products.
+  5. The split rule: the budget without product rounding is far enough below the one with it to tell the two modes apart.
+
+What was seen (this file's prints, `-s`): section 1 -- fixtures with a recipe-A covariance 3.6e-16 - 8.8e-16 on P+, 2.2e-16 -
+3.2e-15 on dx (edge_mixed_spans 4.2e-15 / 1.4e-12, where the oracle itself is 1.0e-12 from the fixture on dx); recipe B 3.5e-16 -
+8.5e-15 on P+, 1.7e-15 - 9.1e-14 on dx; edge_gauge_prior 4.1e-16 / 1.6e-10; windows of 15 / 30 / 53 / 82 clones 6.1e-16 / 6.8e-16 /
+8.9e-16 / 9.1e-16 on P+, <= 1.1e-15 on dx.  Sections 2 - 5: in the tests' own docstrings."""
+import functools
+
+import numpy as np
+import pytest
+
+import f32_model as fm
+import test_gpu_f32 as cases
+from conftest import golden_cases, load_golden, rel_err
+from test_gpu_wide_windows import short_problem
+
+
+# ---- 1. without rounding the model is the oracle ------------------------------------------------------------------------------
+#
+# DESIGN.md 3.3 states the form at 5e-16 on P+ / 2e-14 on dx against the reference's own outputs, figures of one digit from the
+# fixtures of its time (N <= 30: 13 row blocks).  One digit stands for anything up to the next one (5e-16: below 6e-16 ...), and
+# the statement is about the form, not about NumPy's summation order: the bounds here are those figures times 2.  P+ takes
+# one rounding of every entry per row block, so beyond 13 blocks the bound on P+ grows with sqrt(blocks / 13).  Where the
+# reference's own arithmetic is further from the truth than that -- the oracle, the same formulas in the same fp64, differs
+# from the fixture by `own` -- nobody can be closer to the fixture than to the truth: 10 * own.
+MODEL_P, MODEL_DX = 2 * 5e-16, 2 * 2e-14
+RECIPE_B = 1e-12                  # cond(P) ~ 1e18: what test_recipe_b_spectrum_matches_the_reference accepts of the same form
+
+
+def _unrounded(prob, ref_stack):
+    stk = np.hstack([ref_stack["H_X"], ref_stack["r_o"][:, None]])
+    return fm.update(stk, prob.P, prob.sigma, False, False)
+
+
+UPDATE_GOLDENS = [c for c in golden_cases() if int(load_golden(c)[1]["status"]) == 0]
+
+
+@pytest.mark.parametrize("case", UPDATE_GOLDENS)
+def test_without_rounding_the_model_is_the_oracle_on_the_goldens(case):
+    from oracle import msckf_oracle as oracle
+    prob, ref = load_golden(case)
+    o = oracle.update(prob, dense_noise=False)
+    dx, Pn = _unrounded(prob, o)
+    e_dx, e_P = rel_err(dx, ref["dx"]), rel_err(Pn, ref["P_new"])
+    own_dx, own_P = rel_err(o["dx"], ref["dx"]), rel_err(o["P_new"], ref["P_new"])
+    print(f"{case}: model dx {e_dx:.1e} P+ {e_P:.1e} | oracle against the fixture dx {own_dx:.1e} P+ {own_P:.1e}")
+    assert np.array_equal(Pn, Pn.T)
+    tol_dx, tol_P = max(MODEL_DX, 10 * own_dx), max(MODEL_P, 10 * own_P)
+    if case.endswith("_B"):
+        tol_dx, tol_P = RECIPE_B, RECIPE_B
+        ev, ev_ref = np.linalg.eigvalsh(Pn), np.linalg.eigvalsh(ref["P_new"])
+        assert abs(ev - ev_ref).max() < 1e-12 * abs(ev_ref).max()
+    if case == "edge_gauge_prior":
+        # 100 m^2 of prior variance exactly in the stack's null space: dx of the sequential form is what the fp64 ENGINE gives
+        # there too, and test_golden holds that to 1e-8; P+ is at the ordinary level.  (Its fp32 problem: outside the model.)
+        tol_dx = 1e-8
+    assert e_dx < tol_dx and e_P < tol_P
+
+
+@pytest.mark.parametrize("N", [1, 15, 30, 53, 82])
+def test_without_rounding_the_model_is_the_oracle_on_windows(N):
+    from oracle import msckf_oracle as oracle
+    prob = short_problem(N, 6000 + N, F=max(90, 4 * N) if N > 53 else 90)
+    ref = oracle.update(prob, dense_noise=False)
+    stk = fm.stack(prob, ref, np.random.default_rng(N))                # (and in ANY basis of the null spaces)
+    dx, Pn = fm.update(stk, prob.P, prob.sigma, False, False)
+    if N == 1:                                                         # one view per track: no rows, the reference's early return
+        assert ref["status"] == 1 and stk.shape[0] == 0
+        assert np.array_equal(Pn, prob.P) and not dx.any()
+        return
+    assert ref["status"] == 0
+    e_dx, e_P = rel_err(dx, ref["dx"]), rel_err(Pn, ref["P_new"])
+    nb = len(fm.row_blocks(min(stk.shape[0], prob.d)))
+    print(f"N = {N}: {nb} row blocks, model dx {e_dx:.1e} P+ {e_P:.1e}")
+    assert e_dx < MODEL_DX and e_P < MODEL_P * max(1.0, np.sqrt(nb / 13.0))
+
+
+# ---- the cases of tests/test_gpu_f32.py and their budgets, each computed once -------------------------------------------------
+
+def _soak():
+    return cases.soak_case_123()
+
+
+@functools.lru_cache(maxsize=None)
+def _problem(family, key, k=0):
+    """(prob, oracle result) of a case at skip count k."""
+    from oracle import msckf_oracle as oracle
+    if family == "soak":
+        prob = _soak()
+    elif family == "e_short":
+        prob = cases.short_twin(_problem("e", key, k)[0], cases.case_seed("e", key, k))
+    else:
+        prob = cases.make_case(family, key, k)
+    return prob, oracle.update(prob, dense_noise=False)
+
+
+@functools.lru_cache(maxsize=None)
+def _budget(family, key, k, products, first=0):
+    if family == "f":
+        probs, refs = cases.sequence(key, k)
+        b, per = fm.budget_sequence(probs, refs, products, first=first)
+        return b                                                       # [(b_dx, b_P)] per step
+    prob, ref = _problem(family, key, k)
+    if ref["status"] != 0:
+        return None
+    return [fm.budget(prob, ref, products, first=first)[:2]]
+
+
+ALL_CASES = ([("a", N, True) for N in range(1, 54)] + [("b", N, True) for N in range(54, 83)]
+             + [("c30", F, True) for F in cases.PLAN_F] + [("c50", F, True) for F in cases.PLAN_F50]
+             + [("d", i, True) for i in range(len(cases.K5_FORMS))]
+             + [("e", N, False) for N in cases.SPLIT_N] + [("e_short", N, True) for N in cases.SPLIT_N] + [("soak", 0, False)]
+             + [("f", N, True) for N in cases.SEQ_N])
+# one or more cases per family carry the stability check (32 samples)
+STABLE = ([("a", 30, True), ("a", 53, True), ("b", 70, True), ("c30", 241, True), ("c50", 240, True)]
+          + [("d", i, True) for i in range(len(cases.K5_FORMS))]
+          + [("e", N, False) for N in cases.SPLIT_N] + [("soak", 0, False)] + [("f", N, True) for N in cases.SEQ_N])
+
+
+def _skips(family, key):
+    return cases.SEED_SKIPS.get(("e" if family == "e_short" else family, key), 0)
+
+
+def _cap_ok(family, key, k, products):
+    """MARGIN * budget below the flat tolerance, at every step."""
+    if family == "a" and key == 1:
+        return _problem(family, key, k)[1]["status"] == 1             # a window of one clone has no rows: the no-op contract
+    b = _budget(family, key, k, products)
+    return b is not None and all(fm.MARGIN * b_dx < fm.FLAT_DX and fm.MARGIN * b_P < fm.FLAT_P for b_dx, b_P in b)
+
+
+def _stable(family, key, k, products):
+    first, second = _budget(family, key, k, products), _budget(family, key, k, products, first=16)
+    return all(0.5 <= x / y <= 2.0 for a, b in zip(first, second) for x, y in zip(a, b))
+
+
+def _separate(family, key, k):
+    """The P+ budget with product rounding is at least 2 MARGIN times the one without."""
+    (_, t_P), = _budget(family, key, k, True)
+    (_, f_P), = _budget(family, key, k, False)
+    return t_P >= 2 * fm.MARGIN * f_P
+
+
+def _passes(family, key, k, products):
+    ok = _cap_ok(family, key, k, products)
+    if ok and (family, key, products) in STABLE:
+        ok = _stable(family, key, k, products)
+    if ok and family == "e":                                          # the short twin shares the seed; section 5's condition
+        ok = _cap_ok("e_short", key, k, True) and _separate(family, key, k)
+    return ok
+
+
+@pytest.mark.parametrize("family,key,products", ALL_CASES, ids=[f"{f}-{k}" for f, k, _ in ALL_CASES])
+def test_the_cap_does_not_bind(family, key, products):
+    """3. The recorded seed passes and every seed skipped on the way to it does not: "first seed from the base that passes"."""
+    k = _skips(family, key)
+    b = None if (family, key) == ("a", 1) else _budget(family, key, k, products)
+    print(f"{family}/{key} seed skips {k} products={int(products)} budget (dx, P+) per step: {b}")
+    assert _passes(family, key, k, products)
+    if family not in ("soak", "e_short"):
+        for j in range(k):
+            assert not _passes(family, key, j, products)
+
+
+@pytest.mark.parametrize("family,key,products", STABLE, ids=[f"{f}-{k}" for f, k, _ in STABLE])
+def test_the_budget_is_a_stable_statistic(family, key, products):
+    """2. max over samples 1 - 16 against max over samples 17 - 32: within a factor 2, on dx and on P+, at every step."""
+    k = _skips(family, key)
+    first, second = _budget(family, key, k, products), _budget(family, key, k, products, first=16)
+    print(f"{family}/{key}: samples 1-16 {first} | samples 17-32 {second}")
+    assert _stable(family, key, k, products)
+
+
+# ---- 5. the split rule --------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("family,key", [("e", N) for N in cases.SPLIT_N] + [("soak", 0)])
+def test_the_two_product_modes_have_separate_budgets(family, key):
+    """A batch with split long tracks is held to the budget WITHOUT product rounding.  That tells the modes apart where the budget
+    with rounding is at least 2 MARGIN times the one without: it is on P+ (the products are P+'s own rounding) and is not on dx,
+    which the fp32 stack dominates in both modes (ratios 1.7 - 3.5; 14 on the soak case, whose dense remainder blocks are many)
+    -- the GPU test's P+ bound is the one that notices a lost switch.  For the seeded cases this is part of the seed rule."""
+    k = _skips(family, key)
+    (t_dx, t_P), = _budget(family, key, k, True)
+    (f_dx, f_P), = _budget(family, key, k, False)
+    print(f"{family}/{key}: products fp32 (dx, P+) {t_dx:.2e} {t_P:.2e} | fp64 {f_dx:.2e} {f_P:.2e} | ratios {t_dx / f_dx:.1f} {t_P / f_P:.1f}")
+    assert _separate(family, key, k)
+
+
+# ---- 4. the budget can see what the flat tolerance cannot -----------------------------------------------------------------------
+
+def _strips(d):
+    """Index sets of the strips of the augmented state: strip 0 = the 15 IMU entries + the dx row (index d),
+    strip s >= 1 = clone entries 16 (s - 1) ..; the last one is partial when 6 N is no multiple of 16."""
+    out = [np.r_[0:15, d]]
+    for a in range(15, d, 16):
+        out.append(np.arange(a, min(a + 16, d)))
+    return out
+
+
+def drop_term_15_in_the_last_strip(Xa, I):
+    """One of the 16 terms of a rank-16 product lost in the tiles of the partial last strip."""
+    D = fm.f32_product(Xa, I)
+    if Xa.shape[1] == 16:
+        L = _strips(Xa.shape[0] - 1)[-1]
+        x = Xa.astype(np.float32)[:, 15].astype(np.float64)
+        t = np.outer(x, x)
+        mask = np.zeros(D.shape, dtype=bool)
+        mask[L, :] = True; mask[:, L] = True
+        D = D - np.where(mask, t, 0.0)
+    return D
+
+
+def swap_two_rows_in_one_strip(Xa, I):
+    """The tiles of strip 3 with rows 1 and 4 of X_I[3] exchanged: a wrong pi image (pi(1) = 4) in one strip only."""
+    D = fm.f32_product(Xa, I)
+    S = _strips(Xa.shape[0] - 1)[3]
+    Xp = Xa.astype(np.float32)
+    Xs = Xp.copy()
+    Xs[[S[1], S[4]]] = Xp[[S[4], S[1]]]
+    rows = (Xs[S] @ Xp.T).astype(np.float64)
+    D[S, :] = rows
+    D[:, S] = rows.T
+    return D
+
+
+# (the second shape is family e's long-track batch at N = 20: telling fp32 products from fp64 ones is what it was seeded for)
+DEFECT_SHAPES = {"headline": lambda: cases.make_case("c30", 2000), "N20": lambda: _problem("e", 20, _skips("e", 20))[0]}
+
+
+@pytest.mark.parametrize("shape", list(DEFECT_SHAPES))
+def test_the_budget_sees_defects_in_the_products(shape):
+    """On the (30, 2000, 10) headline shape (6 N = 180: a last strip of 4) and on N = 20 (a last strip of 8): each defect's error
+    on P+ is beyond MARGIN * budget.  Printed: whether it is below the flat 1e-5, i.e. whether the flat tolerance alone would
+    have let it through.  Seen: a lost term and swapped rows do NOT stay small -- every later row block works on the damaged
+    covariance, and P+ ends 2e-2 - 2e-1 off, dx 5e-3 - 4e-1: the flat tolerance would have caught both.  Products rounded where
+    fp64 was asked end at 8e-8 (headline) on P+, 7 budgets, and pass the flat tolerance 100 times over: that one only the
+    budget sees."""
+    from oracle import msckf_oracle as oracle
+    prob = DEFECT_SHAPES[shape]()
+    ref = oracle.update(prob, dense_noise=False)
+    assert ref["status"] == 0 and (6 * prob.N) % 16 != 0
+    blks = fm.blocks(prob, ref)
+    b_true = fm.budget(prob, ref, True, S=16, blks=blks)[:2]
+    b_false = fm.budget(prob, ref, False, S=16, blks=blks)[:2]
+    assert fm.MARGIN * b_true[1] < fm.FLAT_P and fm.MARGIN * b_true[0] < fm.FLAT_DX
+    stk = fm.stack(prob, ref, np.random.default_rng([99, 0]), blks)
+    seen = {}
+    for name, product, b in [("a term lost in the last strip", drop_term_15_in_the_last_strip, b_true),
+                             ("two rows swapped in strip 3", swap_two_rows_in_one_strip, b_true),
+                             ("products rounded where fp64 was asked", fm.f32_product, b_false)]:
+        dx, Pn = fm.update(stk, prob.P, prob.sigma, True, True, product=product)
+        e_dx, e_P = rel_err(dx, ref["dx"]), rel_err(Pn, ref["P_new"])
+        seen[name] = (e_P, b[1])
+        print(f"{shape}: {name}: P+ {e_P:.2e} = {e_P / b[1]:.0f} budgets ({b[1]:.2e}), dx {e_dx:.2e} = {e_dx / b[0]:.1f} budgets; "
+              f"{'PASSES' if e_P < fm.FLAT_P and e_dx < fm.FLAT_DX else 'fails'} the flat tolerance")
+    for name, (e_P, b_P) in seen.items():
+        assert e_P > fm.MARGIN * b_P, name

@@ -40,6 +40,10 @@
 #include "k_tracks.h"
 #include "k_match.h"
 #include "run_outcome.h"
+#include "track_mirror.h"
+
+static_assert(TrackMirror::kOk == MSCKF_OK && TrackMirror::kErrArg == MSCKF_ERR_ARG && TrackMirror::kErrDupSlot == MSCKF_ERR_DUP_SLOT,
+              "track_mirror.h returns the ABI's codes");
 
 using namespace msckf;
 
@@ -484,27 +488,21 @@ struct msckf_ctx {
     bool run_pending = false;                    // ... a pipeline / merge among it (kernels that read the K5 plan and the workspace)
     bool wide_concurrent = true;          // MSCKF_WIDE_STREAM=0: everything on one stream
     // The track store (k_tracks.h): the floating-point fields of the tracks in HBM, which track has views in which clone slots
-    // here.  Rows are handed out by this mirror; a row's views are in ascending slot order (they are appended for the newest
-    // clone and the renumbering of msckf_remove_clones is monotone).
+    // here (track_mirror.h).  Rows are handed out by the mirror; a row's views are in ascending slot order (they are appended for
+    // the newest clone and the renumbering of msckf_remove_clones is monotone).
     Buf dTrk, dTrkRows, dTrkRowSorted;
     TrackStore trk{};
-    bool trk_ready = false;
-    std::vector<int> trk_id, trk_M, trk_anchor, trk_slots;   // per row: id (-1: free), views, anchor slot (-1: frozen), [row][V] slots
-    std::vector<int> trk_lost, trk_tracked;                  // per row: lost_for_n_frames / tracked_for_n_frames (MSCKF.py:400, :411-412, :438)
-    std::vector<long long> trk_seq;                          // per row: when the track was created (rows are recycled; the reference's dict order)
-    long long trk_next_seq = 0;
-    std::vector<int> trk_free, trk_dropped;                  // free rows (a stack); ids the last msckf_remove_clones deleted
-    std::unordered_map<int, int> trk_row_of;                 // id -> row
-    long long trk_views = 0;
+    bool trk_ready = false;               // the device arrays are allocated and the mirror is sized
+    TrackMirror mirror;
+    std::vector<TrackPlace> trk_plan;     // the places of the intake at hand (TrackMirror::plan)
     bool batch_from_store = false;        // the current batch came through msckf_tracks_load: msckf_run_select writes refreshed points back
     PinStage trk_obs_stage, trk_load_stage, trk_frame_stage;
     // descriptors behind the store (k_match.h): per-view rows and one match row per track, allocated by the first call that
-    // brings descriptors.  trk_hasdesc: every view of the row came with one (msckf_tracks_match_frame made them all).
+    // brings descriptors.
     Buf dDescViews, dDescRow, dMatch;
     DescStore desc{};
     bool desc_ready = false;
     int desc_D = 0;                       // the store's descriptor dimension; 0: not set yet
-    std::vector<char> trk_hasdesc;
     PinStage trk_match_stage, trk_desc_stage;
     long fetched_serial = -1;             // the run whose return code msckf_get_result derived last ...
     int fetched_rc = 0;                   // ... and that code: msckf_commit_covariance need not read the gate results again
@@ -2133,21 +2131,9 @@ int stage_release(msckf_ctx* c, PinStage& s) {
 }
 
 void tracks_clear(msckf_ctx* c) {
-    c->trk_row_of.clear();
-    c->trk_dropped.clear();
-    c->trk_views = 0;
+    c->mirror.clear();
     c->batch_from_store = false;
     c->desc_D = 0;
-    if (!c->trk_ready) return;
-    const int T = c->maxF;
-    std::fill(c->trk_hasdesc.begin(), c->trk_hasdesc.end(), 0);
-    std::fill(c->trk_id.begin(), c->trk_id.end(), -1);
-    std::fill(c->trk_M.begin(), c->trk_M.end(), 0);
-    std::fill(c->trk_lost.begin(), c->trk_lost.end(), 0);
-    std::fill(c->trk_tracked.begin(), c->trk_tracked.end(), 0);
-    c->trk_next_seq = 0;
-    c->trk_free.resize(T);
-    for (int r = 0; r < T; ++r) c->trk_free[r] = T - 1 - r;         // row 0 goes out first
 }
 
 // capacity max_features tracks x max_track views, allocated on first use
@@ -2165,23 +2151,14 @@ int tracks_ensure(msckf_ctx* c) {
     s.rho = reinterpret_cast<double*>(b + o_rho); s.frozen = reinterpret_cast<double*>(b + o_frozen);
     s.slot = reinterpret_cast<int*>(b + o_slot); s.anchor = reinterpret_cast<int*>(b + o_anchor);
     s.count = reinterpret_cast<int*>(b + o_count); s.V = (int)V;
-    c->trk_id.assign(T, -1); c->trk_M.assign(T, 0); c->trk_anchor.assign(T, -1); c->trk_slots.assign(TV, 0);
-    c->trk_lost.assign(T, 0); c->trk_tracked.assign(T, 0); c->trk_seq.assign(T, 0);
-    c->trk_hasdesc.assign(T, 0);
+    c->mirror.size((int)T, (int)V);
     c->trk_ready = true;
     tracks_clear(c);
     return MSCKF_OK;
 }
 
-inline void tracks_free_row(msckf_ctx* c, int row) {
-    c->trk_row_of.erase(c->trk_id[row]);
-    c->trk_views -= c->trk_M[row];
-    c->trk_id[row] = -1; c->trk_M[row] = 0;
-    c->trk_lost[row] = c->trk_tracked[row] = 0;                     // the counters die with the track
-    c->trk_hasdesc[row] = 0;
-    c->trk_free.push_back(row);
-    c->batch_from_store = false;          // (the row may be handed out again: a loaded batch no longer writes refreshed points back)
-}
+// the mirror freed rows, which may be handed out again: a loaded batch no longer writes refreshed points back
+inline void tracks_rows_freed(msckf_ctx* c, size_t n) { if (n > 0) c->batch_from_store = false; }
 
 int launch_track_emit(msckf_ctx* c, const TrackEmitSrc* src, int F, int sumM, const int32_t* view_ptr,
                       const std::vector<int>& h_view, char* draw, size_t r_base, size_t r_m, size_t r_rho, size_t r_slot) {
@@ -2222,14 +2199,12 @@ bool assoc_kinv(const double* K, double* Kinv) {
 
 // msckf_remove_clones on a context whose store holds tracks (reference MSCKF.py:760-779): drop[s] != 0 for the clones that go
 int tracks_drop_clones(msckf_ctx* c, const std::vector<char>& drop) {
-    c->trk_dropped.clear();
-    if (!c->trk_ready || c->trk_row_of.empty()) return MSCKF_OK;
-    const int N = c->N, V = c->maxV;
+    c->mirror.forget_dropped();
+    if (c->mirror.n_tracks() == 0) return MSCKF_OK;
     TrackDropArgs a{};
-    for (int s = 0, k = 0; s < N; ++s) a.remap[s] = drop[s] ? (short)-1 : (short)k++;
+    for (int s = 0, k = 0; s < c->N; ++s) a.remap[s] = drop[s] ? (short)-1 : (short)k++;
     std::vector<int> rows;
-    rows.reserve(c->trk_row_of.size());
-    for (int r = 0; r < c->maxF; ++r) if (c->trk_id[r] >= 0) rows.push_back(r);
+    c->mirror.live_rows(rows);
     a.s = c->trk; a.rows = ptr<int>(c->dTrkRows); a.n = (int)rows.size(); a.cam_t = ptr<double>(c->dCamT);
     HIPCHK(c, hipMemcpyAsync(c->dTrkRows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (c->desc_ready) {                  // the descriptor views first: k_desc_drop reads the slots k_track_drop renumbers
@@ -2239,15 +2214,8 @@ int tracks_drop_clones(msckf_ctx* c, const std::vector<char>& drop) {
     hipLaunchKernelGGL(k_track_drop, dim3((a.n + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));                     // (`rows` is pageable memory; the call is a blocking one anyway)
-    for (int r : rows) {
-        int* sl = &c->trk_slots[(size_t)r * V];
-        int M = 0;
-        for (int v = 0; v < c->trk_M[r]; ++v) if (a.remap[sl[v]] >= 0) sl[M++] = a.remap[sl[v]];
-        c->trk_views -= c->trk_M[r] - M;
-        c->trk_M[r] = M;
-        if (c->trk_anchor[r] >= 0) c->trk_anchor[r] = a.remap[c->trk_anchor[r]];
-        if (M == 0) { c->trk_dropped.push_back(c->trk_id[r]); tracks_free_row(c, r); }
-    }
+    c->mirror.drop_clones(a.remap);
+    tracks_rows_freed(c, c->mirror.dropped().size());
     return MSCKF_OK;
 }
 
@@ -3644,10 +3612,9 @@ int msckf_commit_inject(msckf_ctx* c) {
 // the batch of the listed rows (input order) with these counters: msckf_set_features + msckf_set_tracks from the store
 static int tracks_load_rows(msckf_ctx* c, int F, const std::vector<int>& rows, const std::vector<int>& view_ptr,
                             const int32_t* lost_for, const int32_t* tracked_for) {
-    const int V = c->maxV;
     std::vector<int> slots(view_ptr[F]);
     for (int f = 0; f < F; ++f)
-        std::memcpy(slots.data() + view_ptr[f], &c->trk_slots[(size_t)rows[f] * V], (size_t)c->trk_M[rows[f]] * 4);
+        std::memcpy(slots.data() + view_ptr[f], c->mirror.slots(rows[f]), (size_t)c->mirror.M(rows[f]) * 4);
     const TrackEmitSrc src{rows.data(), lost_for, tracked_for};
     const int rc = set_features_impl(c, F, view_ptr.data(), nullptr, slots.data(), nullptr, nullptr, nullptr, &src);
     if (rc != MSCKF_OK) return rc;
@@ -3669,40 +3636,16 @@ int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const doub
     if (!ids || !uv || !score) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = tracks_ensure(c)) return rc;
-    const int newest = c->N - 1, V = c->maxV;
+    const int newest = c->N - 1;
     // every check first: an erroring call leaves the store exactly as it was
-    {
-        std::unordered_set<int> seen;
-        size_t fresh = 0;
-        for (int i = 0; i < n; ++i) {
-            if (ids[i] < 0) return MSCKF_ERR_ARG;
-            if (!seen.insert(ids[i]).second) return MSCKF_ERR_DUP_SLOT;
-            const auto it = c->trk_row_of.find(ids[i]);
-            if (it == c->trk_row_of.end()) { ++fresh; continue; }
-            const int r = it->second, M = c->trk_M[r];
-            if (M > 0 && c->trk_slots[(size_t)r * V + M - 1] == newest) return MSCKF_ERR_DUP_SLOT;
-            if (M + 1 > V) return MSCKF_ERR_ARG;
-        }
-        if (fresh > c->trk_free.size()) return MSCKF_ERR_ARG;
-    }
+    c->trk_plan.resize(n);
+    const TrackPlace* place = c->trk_plan.data();
+    if (int rc = c->mirror.plan(ids, n, newest, c->trk_plan.data())) return rc;
     if (int rc = stage_acquire(c, c->trk_obs_stage, (size_t)n * sizeof(TrackObsRec))) return rc;
     TrackObsRec* rec = static_cast<TrackObsRec*>(c->trk_obs_stage.p);
     for (int i = 0; i < n; ++i) {
-        const auto it = c->trk_row_of.find(ids[i]);
-        int r, fresh = 0;
-        if (it == c->trk_row_of.end()) {
-            r = c->trk_free.back(); c->trk_free.pop_back();
-            c->trk_row_of.emplace(ids[i], r);
-            c->trk_id[r] = ids[i]; c->trk_M[r] = 0; c->trk_anchor[r] = newest;
-            c->trk_seq[r] = c->trk_next_seq++;
-            fresh = 1;
-        } else r = it->second;
-        ++c->trk_tracked[r]; c->trk_lost[r] = 0;                    // an append (MSCKF.py:411-412)
-        c->trk_hasdesc[r] = 0;                                      // (a view without a descriptor)
-        const int pos = c->trk_M[r]++;
-        c->trk_slots[(size_t)r * V + pos] = newest;
-        ++c->trk_views;
-        rec[i] = TrackObsRec{r, pos, fresh, 0, uv[2 * i], uv[2 * i + 1], score[i]};
+        c->mirror.commit(ids[i], place[i], newest, true, false);    // every pair is an append, without a descriptor
+        rec[i] = TrackObsRec{place[i].row, place[i].pos, place[i].fresh, 0, uv[2 * i], uv[2 * i + 1], score[i]};
     }
     TrackObsArgs a{};
     a.s = c->trk; a.rec = rec; a.n = n; a.slot = newest;
@@ -3716,10 +3659,8 @@ int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const doub
 
 int msckf_tracks_remove(msckf_ctx* c, int32_t n, const int32_t* ids) {
     if (!c || n < 0 || (n > 0 && !ids)) return MSCKF_ERR_ARG;
-    std::unordered_set<int> seen;
-    for (int i = 0; i < n; ++i)
-        if (!c->trk_row_of.count(ids[i]) || !seen.insert(ids[i]).second) return MSCKF_ERR_ARG;
-    for (int i = 0; i < n; ++i) tracks_free_row(c, c->trk_row_of[ids[i]]);
+    if (int rc = c->mirror.remove(ids, n)) return rc;
+    tracks_rows_freed(c, (size_t)n);
     return MSCKF_OK;
 }
 
@@ -3731,10 +3672,9 @@ int msckf_tracks_load(msckf_ctx* c, int32_t F, const int32_t* ids, const int32_t
     {
         std::unordered_set<int> seen;
         for (int f = 0; f < F; ++f) {
-            const auto it = c->trk_row_of.find(ids[f]);
-            if (it == c->trk_row_of.end() || !seen.insert(ids[f]).second) return MSCKF_ERR_ARG;
-            rows[f] = it->second;
-            view_ptr[f + 1] = view_ptr[f] + c->trk_M[rows[f]];
+            rows[f] = c->mirror.row_of(ids[f]);
+            if (rows[f] < 0 || !seen.insert(ids[f]).second) return MSCKF_ERR_ARG;
+            view_ptr[f + 1] = view_ptr[f] + c->mirror.M(rows[f]);
         }
     }
     return tracks_load_rows(c, F, rows, view_ptr, lost_for, tracked_for);
@@ -3749,38 +3689,22 @@ static int tracks_frame_impl(msckf_ctx* c, const msckf_frame_params* fp, int32_t
     if (n > 0 && (!ids || !uv || !score || !result)) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = tracks_ensure(c)) return rc;
-    const int newest = c->N - 1, V = c->maxV, T = c->maxF;
+    const int newest = c->N - 1;
     TrackFrameArgs a{};
     if (!assoc_kinv(fp->K, a.Kinv_test)) return MSCKF_ERR_ARG;
     // every check first: an erroring call leaves the store and the counters exactly as they were
-    {
-        std::unordered_set<int> seen;
-        size_t fresh = 0;
-        for (int i = 0; i < n; ++i) {
-            if (ids[i] < 0 || !std::isfinite(uv[2 * i]) || !std::isfinite(uv[2 * i + 1])) return MSCKF_ERR_ARG;
-            if (!seen.insert(ids[i]).second) return MSCKF_ERR_DUP_SLOT;
-            const auto it = c->trk_row_of.find(ids[i]);
-            if (it == c->trk_row_of.end()) { ++fresh; continue; }
-            const int r = it->second, M = c->trk_M[r];
-            if (M > 0 && c->trk_slots[(size_t)r * V + M - 1] == newest) return MSCKF_ERR_DUP_SLOT;
-            if (M + 1 > V) return MSCKF_ERR_ARG;
-        }
-        if (fresh > c->trk_free.size()) return MSCKF_ERR_ARG;
-    }
-    std::vector<char> listed(T, 0);
+    c->trk_plan.resize(n);
+    const TrackPlace* place = c->trk_plan.data();
+    if (int rc = c->mirror.plan(ids, n, newest, c->trk_plan.data(), nullptr,
+                                [uv](int i) { return std::isfinite(uv[2 * i]) && std::isfinite(uv[2 * i + 1]); })) return rc;
     if (n > 0) {
         // the image: n records the kernel reads | n failing views | n result bytes it writes
         const size_t o_fv = (size_t)n * sizeof(TrackObsRec), o_res = o_fv + (size_t)n * 4;
         if (int rc = stage_acquire(c, c->trk_frame_stage, o_res + (size_t)n)) return rc;
         char* img = static_cast<char*>(c->trk_frame_stage.p);
         TrackObsRec* rec = reinterpret_cast<TrackObsRec*>(img);
-        size_t taken = 0;                 // fresh pairs take the rows the free stack hands out next, in the listed order
-        for (int i = 0; i < n; ++i) {
-            const auto it = c->trk_row_of.find(ids[i]);
-            const bool fresh = it == c->trk_row_of.end();
-            const int r = fresh ? c->trk_free[c->trk_free.size() - 1 - taken++] : it->second;
-            rec[i] = TrackObsRec{r, fresh ? 0 : c->trk_M[r], fresh ? 1 : 0, 0, uv[2 * i], uv[2 * i + 1], score[i]};
-        }
+        for (int i = 0; i < n; ++i)
+            rec[i] = TrackObsRec{place[i].row, place[i].pos, place[i].fresh, 0, uv[2 * i], uv[2 * i + 1], score[i]};
         a.s = c->trk; a.rec = rec; a.n = n; a.slot = newest;
         a.cam_R = ptr<double>(c->dCamR); a.cam_t = ptr<double>(c->dCamT);
         std::memcpy(a.K, fp->K, sizeof(a.K));
@@ -3791,27 +3715,13 @@ static int tracks_frame_impl(msckf_ctx* c, const msckf_frame_params* fp, int32_t
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));                 // the mirror needs the results: the call blocks
         for (int i = 0; i < n; ++i) {
-            const TrackObsRec& q = rec[i];
-            const int r = q.row, res = a.result[i];
-            listed[r] = 1;
+            const int res = a.result[i];
             result[i] = (uint8_t)res;
             if (fail_view) fail_view[i] = a.fail_view[i];
-            if (q.fresh) {
-                c->trk_free.pop_back();
-                c->trk_row_of.emplace(ids[i], r);
-                c->trk_id[r] = ids[i]; c->trk_M[r] = 0; c->trk_anchor[r] = newest;
-                c->trk_seq[r] = c->trk_next_seq++;
-                c->trk_tracked[r] = 0; c->trk_lost[r] = 0;
-                c->trk_hasdesc[r] = with_desc;
-            }
-            if (res == 1 || res == 2) { ++c->trk_lost[r]; continue; }               // MSCKF.py:400
-            if (!with_desc) c->trk_hasdesc[r] = 0;
-            c->trk_slots[(size_t)r * V + c->trk_M[r]++] = newest;                    // appended (:403-421) or created (:424-436)
-            ++c->trk_views;
-            ++c->trk_tracked[r]; c->trk_lost[r] = 0;                                 // :411-412
+            c->mirror.commit(ids[i], place[i], newest, res != 1 && res != 2, with_desc);   // 1, 2: a test failed (MSCKF.py:400)
         }
     }
-    for (int r = 0; r < T; ++r) if (c->trk_id[r] >= 0 && !listed[r]) ++c->trk_lost[r];   // not matched in this frame (:438)
+    c->mirror.age_unlisted(place, n);     // not matched in this frame (:438)
     return MSCKF_OK;
 }
 
@@ -3838,16 +3748,8 @@ static int match_check(msckf_ctx* c, int32_t D, int32_t n, const float* desc, st
     if (D < 1 || D > DESC_DIM || (c->desc_D != 0 && D != c->desc_D)) return MSCKF_ERR_ARG;
     if (n > 0 && !desc) return MSCKF_ERR_ARG;
     for (size_t i = 0; i < (size_t)n * D; ++i) if (!std::isfinite(desc[i])) return MSCKF_ERR_ARG;
-    rows.clear();
-    if (!c->trk_ready) return MSCKF_OK;
-    std::vector<std::pair<long long, int>> live;
-    for (int r = 0; r < c->maxF; ++r) {
-        if (c->trk_id[r] < 0) continue;
-        if (!c->trk_hasdesc[r]) { c->last_error = "track store: a track holds a view without a descriptor"; return MSCKF_ERR_STATE; }
-        live.emplace_back(c->trk_seq[r], r);
-    }
-    std::sort(live.begin(), live.end());
-    for (const auto& e : live) rows.push_back(e.second);
+    if (!c->mirror.all_have_desc()) { c->last_error = "track store: a track holds a view without a descriptor"; return MSCKF_ERR_STATE; }
+    c->mirror.live_rows_by_creation(rows);
     return MSCKF_OK;
 }
 
@@ -3899,7 +3801,7 @@ int msckf_tracks_match(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = match_run(c, min_cos, D, n, desc, rows, pair, sim)) return rc;
     for (size_t t = 0; t < rows.size(); ++t)
-        if (pair[t] >= 0) { track_id_out[pair[t]] = c->trk_id[rows[t]]; if (sim_out) sim_out[pair[t]] = sim[t]; }
+        if (pair[t] >= 0) { track_id_out[pair[t]] = c->mirror.id(rows[t]); if (sim_out) sim_out[pair[t]] = sim[t]; }
     return MSCKF_OK;
 }
 
@@ -3921,14 +3823,14 @@ int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t
     std::vector<float> ksim(n, 0.f);
     int matched = 0;
     for (size_t t = 0; t < rows.size(); ++t)
-        if (pair[t] >= 0) { ids[pair[t]] = c->trk_id[rows[t]]; ksim[pair[t]] = sim[t]; ++matched; }
+        if (pair[t] >= 0) { ids[pair[t]] = c->mirror.id(rows[t]); ksim[pair[t]] = sim[t]; ++matched; }
     if (!empty && matched == 0) return MSCKF_NOOP;                   // :320: the frame is skipped as a whole
     {
         // ids in ascending keypoint order (np.setdiff1d, FeatureExtractor.py:72); they may not reach past int32 or hit a live id
         long long next = mp->first_new_id;
         for (int j = 0; j < n; ++j) {
             if (ids[j] >= 0) continue;
-            if (next > 0x7fffffffLL || c->trk_row_of.count((int)next)) return MSCKF_ERR_ARG;
+            if (next > 0x7fffffffLL || c->mirror.row_of((int)next) >= 0) return MSCKF_ERR_ARG;
             ids[j] = (int32_t)next++;
         }
     }
@@ -3939,7 +3841,7 @@ int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t
     if (int rc = tracks_frame_impl(c, &fp, n, ids.data(), uv, score, result, fv.data(), true)) return rc;
     // the descriptors of the views that went in, then every row anew (:436-441)
     std::vector<int> all;
-    for (int r = 0; r < c->maxF; ++r) if (c->trk_id[r] >= 0) all.push_back(r);
+    c->mirror.live_rows(all);
     const size_t o_all = (size_t)n * sizeof(DescRec);
     if (int rc = stage_acquire(c, c->trk_desc_stage, o_all + all.size() * 4)) return rc;
     char* img = static_cast<char*>(c->trk_desc_stage.p);
@@ -3947,8 +3849,8 @@ int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t
     int nrec = 0;
     for (int j = 0; j < n; ++j) {
         if (result[j] != 0 && result[j] != 4) continue;
-        const int r = c->trk_row_of[ids[j]];
-        rec[nrec++] = DescRec{r, c->trk_M[r] - 1, j, 0};
+        const int r = c->mirror.row_of(ids[j]);
+        rec[nrec++] = DescRec{r, c->mirror.M(r) - 1, j, 0};
     }
     std::memcpy(img + o_all, all.data(), all.size() * 4);
     if (nrec) hipLaunchKernelGGL(k_desc_store, dim3(nrec), dim3(64), 0, c->stream, c->desc, (const DescRec*)rec, (const float*)ptr<float>(c->dMatch));
@@ -3967,13 +3869,13 @@ int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t
 
 int msckf_tracks_descriptor(msckf_ctx* c, int32_t id, float* row, int32_t* M_out, float* views) {
     if (!c) return MSCKF_ERR_ARG;
-    const auto it = c->trk_row_of.find(id);
-    if (it == c->trk_row_of.end()) return MSCKF_ERR_ARG;
-    const size_t r = it->second, V = c->maxV;
-    if (!c->desc_ready || !c->trk_hasdesc[r]) return MSCKF_ERR_STATE;
+    const int at = c->mirror.row_of(id);
+    if (at < 0) return MSCKF_ERR_ARG;
+    const size_t r = at, V = c->maxV;
+    if (!c->desc_ready || !c->mirror.hasdesc(at)) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int M = c->trk_M[r], D = c->desc_D;
+    const int M = c->mirror.M(at), D = c->desc_D;
     std::vector<float> hrow(DESC_DIM), hv((size_t)std::max(M, 1) * DESC_DIM);
     HIPCHK(c, hipMemcpy(hrow.data(), c->desc.row + r * DESC_DIM, DESC_DIM * 4, hipMemcpyDeviceToHost));
     if (M) HIPCHK(c, hipMemcpy(hv.data(), c->desc.views + r * V * DESC_DIM, (size_t)M * DESC_DIM * 4, hipMemcpyDeviceToHost));
@@ -3991,37 +3893,30 @@ int msckf_tracks_load_where(msckf_ctx* c, int32_t n_slots, const int32_t* slots,
         if (slots[i] < 0 || slots[i] >= c->N) return MSCKF_ERR_ARG;
         want[slots[i]] = 1;
     }
-    const int V = c->maxV;
-    std::vector<std::pair<long long, int>> cand;                    // (creation number, row): the reference's dict order
-    if (c->trk_ready)
-        for (int r = 0; r < c->maxF; ++r) {
-            if (c->trk_id[r] < 0) continue;
-            bool hit = n_slots == 0;
-            for (int v = 0; !hit && v < c->trk_M[r]; ++v) hit = want[c->trk_slots[(size_t)r * V + v]];
-            if (hit) cand.emplace_back(c->trk_seq[r], r);
-        }
-    std::sort(cand.begin(), cand.end());
-    const int F = (int)cand.size();
+    std::vector<int> rows;                                          // in creation order: the reference's dict order
+    if (n_slots == 0) c->mirror.live_rows_by_creation(rows);
+    else c->mirror.live_rows_by_creation(want, rows);
+    const int F = (int)rows.size();
     if (F > cap) return MSCKF_ERR_ARG;
-    std::vector<int> rows(F), view_ptr(F + 1, 0), lost(F), tracked(F);
+    std::vector<int> view_ptr(F + 1, 0), lost(F), tracked(F);
     for (int f = 0; f < F; ++f) {
-        const int r = cand[f].second;
-        rows[f] = r; lost[f] = c->trk_lost[r]; tracked[f] = c->trk_tracked[r];
-        view_ptr[f + 1] = view_ptr[f] + c->trk_M[r];
+        const int r = rows[f];
+        lost[f] = c->mirror.lost(r); tracked[f] = c->mirror.tracked(r);
+        view_ptr[f + 1] = view_ptr[f] + c->mirror.M(r);
     }
     if (int rc = tracks_load_rows(c, F, rows, view_ptr, lost.data(), tracked.data())) return rc;
-    for (int f = 0; f < F; ++f) ids_out[f] = c->trk_id[rows[f]];
+    for (int f = 0; f < F; ++f) ids_out[f] = c->mirror.id(rows[f]);
     *F_out = F;
     return MSCKF_OK;
 }
 
 int msckf_tracks_counters(msckf_ctx* c, int32_t n, const int32_t* ids, int32_t* lost_for, int32_t* tracked_for) {
     if (!c || n < 0 || (n > 0 && !ids)) return MSCKF_ERR_ARG;
-    for (int i = 0; i < n; ++i) if (!c->trk_row_of.count(ids[i])) return MSCKF_ERR_ARG;
+    for (int i = 0; i < n; ++i) if (c->mirror.row_of(ids[i]) < 0) return MSCKF_ERR_ARG;
     for (int i = 0; i < n; ++i) {
-        const int r = c->trk_row_of[ids[i]];
-        if (lost_for) lost_for[i] = c->trk_lost[r];
-        if (tracked_for) tracked_for[i] = c->trk_tracked[r];
+        const int r = c->mirror.row_of(ids[i]);
+        if (lost_for) lost_for[i] = c->mirror.lost(r);
+        if (tracked_for) tracked_for[i] = c->mirror.tracked(r);
     }
     return MSCKF_OK;
 }
@@ -4030,22 +3925,21 @@ int msckf_tracks_clone_views(msckf_ctx* c, int32_t* views) {
     if (!c || (c->N > 0 && !views)) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     for (int s = 0; s < c->N; ++s) views[s] = 0;
-    if (!c->trk_ready) return MSCKF_OK;
-    const int V = c->maxV;
-    for (int r = 0; r < c->maxF; ++r)
-        if (c->trk_id[r] >= 0)
-            for (int v = 0; v < c->trk_M[r]; ++v) ++views[c->trk_slots[(size_t)r * V + v]];
+    std::vector<int> rows;
+    c->mirror.live_rows(rows);
+    for (int r : rows)
+        for (int v = 0; v < c->mirror.M(r); ++v) ++views[c->mirror.slots(r)[v]];
     return MSCKF_OK;
 }
 
 int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, double* uv, double* dir, double* conf,
                      double* line_base, double* idp_base, double* idp_m, double* idp_rho, int32_t* anchor_slot) {
     if (!c) return MSCKF_ERR_ARG;
-    const auto it = c->trk_row_of.find(id);
-    if (it == c->trk_row_of.end()) return MSCKF_ERR_ARG;
+    const int row = c->mirror.row_of(id);
+    if (row < 0) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t r = it->second, V = c->maxV, N = c->N;
-    const int M = c->trk_M[r];
+    const size_t r = row, V = c->maxV, N = c->N;
+    const int M = c->mirror.M(row);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const TrackStore& s = c->trk;
     std::vector<int> sl(V);
@@ -4063,9 +3957,7 @@ int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, d
     HIPCHK(c, hipMemcpy(&count, s.count + r, 4, hipMemcpyDeviceToHost));
     if (N > 0) HIPCHK(c, hipMemcpy(camt.data(), c->dCamT.p, N * 24, hipMemcpyDeviceToHost));
     // the integers are the device's; the mirror must agree with them
-    bool same = count == M && anchor == c->trk_anchor[r] && anchor < (int)N;
-    for (int v = 0; same && v < M; ++v) same = sl[v] == c->trk_slots[r * V + v] && sl[v] >= 0 && sl[v] < (int)N;
-    if (!same) { c->last_error = "track store: the device rows and the host mirror differ"; return MSCKF_ERR_STATE; }
+    if (!c->mirror.agrees(row, count, anchor, sl.data(), (int)N)) { c->last_error = "track store: the device rows and the host mirror differ"; return MSCKF_ERR_STATE; }
     if (M_out) *M_out = M;
     if (slots) std::memcpy(slots, sl.data(), (size_t)M * 4);
     if (uv) std::memcpy(uv, huv.data(), (size_t)M * 16);
@@ -4081,15 +3973,15 @@ int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, d
 
 int msckf_tracks_count(msckf_ctx* c, int32_t* n_tracks, int32_t* n_views) {
     if (!c) return MSCKF_ERR_ARG;
-    if (n_tracks) *n_tracks = (int32_t)c->trk_row_of.size();
-    if (n_views) *n_views = (int32_t)c->trk_views;
+    if (n_tracks) *n_tracks = (int32_t)c->mirror.n_tracks();
+    if (n_views) *n_views = (int32_t)c->mirror.n_views();
     return MSCKF_OK;
 }
 
 int msckf_tracks_dropped(msckf_ctx* c, int32_t* ids, int32_t cap) {
     if (!c || cap < 0 || (cap > 0 && !ids)) return MSCKF_ERR_ARG;
-    const int n = (int)c->trk_dropped.size();
-    if (n > 0 && cap > 0) std::memcpy(ids, c->trk_dropped.data(), (size_t)std::min(n, (int)cap) * 4);
+    const int n = (int)c->mirror.dropped().size();
+    if (n > 0 && cap > 0) std::memcpy(ids, c->mirror.dropped().data(), (size_t)std::min(n, (int)cap) * 4);
     return n;
 }
 

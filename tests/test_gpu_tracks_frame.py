@@ -329,6 +329,9 @@ def test_error_codes_leave_store_and_counters_as_they_were():
         assert code([8], np.array([[1.0, np.inf]])) == _ffi.ERR_ARG
         assert code([8, 9], uv[[3, 3], 4]) == _ffi.ERR_ARG           # four rows, three in use
         assert code([8, 1], uv[[3, 0], 4]) == _ffi.ERR_ARG           # 1 holds max_track views already
+        bad_uv = np.array([uv[2, 4], [np.nan, 1.0]])                 # the first offending pair in list order decides the code
+        assert code([3, 8], bad_uv) == _ffi.ERR_DUP_SLOT             # 3 is in the newest clone already; then a uv that is not finite
+        assert code([8, 3], bad_uv[::-1]) == _ffi.ERR_ARG            # ... the two pairs swapped
         with pytest.raises(_ffi.EngineError) as err:
             eng.tracks_counters([1, 77])
         assert err.value.code == _ffi.ERR_ARG

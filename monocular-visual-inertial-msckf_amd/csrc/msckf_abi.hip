@@ -285,6 +285,24 @@ struct RunRecord {
 
 }  // namespace
 
+// A sweep node's schedule and tables depend on its folds' shapes, not on where its sources lie or how many tracks they hold:
+// a window's group shape repeats from batch to batch, and most merge nodes of one plan share a shape.  Kept by the exact inputs
+// (key: wtot, fold slots, adopted, gate table wanted, then off, w, ew, prod, ld of every fold), so a hit IS the table a rebuild gives.
+struct SweepTables {
+    std::vector<int> key;
+    std::vector<int> t0;                  // SweepFold::t0 of the folds (sweep_schedule)
+    int nsteps = 0;
+    std::vector<int> tab;                 // sweep_flush_table, then sweep_gate_table where the key asks for it
+    int n_gate = -1;                      // ... its step-0 requirements; -1: no gate table
+};
+struct SweepMemo {
+    static constexpr int CAP = 64;
+    std::vector<SweepTables> e;           // up to CAP, the oldest replaced first
+    int next = 0;
+    int at[CAP];                          // where the entry's table sits in the plan being built, -1: not in it yet
+    std::vector<int> key;                 // (scratch)
+};
+
 struct msckf_ctx {
     msckf_config cfg{};
     int device = 0;
@@ -343,6 +361,16 @@ struct msckf_ctx {
     bool leaf_narrow = false, leaf_wide = false;      // band plan: leaf nodes with w + 1 <= 64 / > 64 exist
     size_t root_off = 0;                  // offset (doubles) of the root block [T | r_n] in rbuf
     size_t zero_off = 0;                  // 16 doubles of the workspace no kernel writes: they read 0.0
+    // Band plans in k_sweep form without group exchange or split long tracks keep the root block and the zero words at the HEAD of
+    // the workspace, at offsets that depend on dc alone: the only entries a kernel reads without writing them in the same run
+    // (DESIGN.md 3.2).  Cleared once per (allocation, dc), they stay valid from plan to plan: a plan miss clears nothing.
+    bool ws_head = false;                 // the current plan has that layout
+    bool ws_key_valid = false;            // the head of the workspace at ws_key_p was cleared for ws_key_dc and only such plans ran since
+    const void* ws_key_p = nullptr;
+    int ws_key_dc = 0;
+    bool ws_poison = false;               // MSCKF_DEBUG_POISON=1: NaN in every new workspace and wherever a plan miss skips the clear
+    bool plan_memo = true;                // MSCKF_PLAN_MEMO=0: the planner rebuilds the root's and the merge nodes' tables on every miss
+    SweepMemo memo;                       // schedules and flush / gate tables of sweep nodes by their folds (sweep_tables)
     // group exchange (sharded band pipeline): the group triangles live in one export record at the head of rbuf
     bool xchg = false;                    // requested by msckf_set_group_exchange
     int xchg_span = 0;                    // longest track of the WHOLE batch in clone slots (msckf_set_exchange_span); 0: not told
@@ -444,14 +472,16 @@ struct msckf_ctx {
     hipStream_t stream2 = nullptr;        // the long tracks' kernels (k_feature<64, true>, k_rem_scatter, the remainder blocks' tree) run beside the band pipeline
     hipEvent_t ev_fork = nullptr, ev_wfeat = nullptr;   // uploads done -> stream2 may start; the wide tracks' K4 blocks are written
     bool wide_on_stream2 = false;         // this batch's wide k_feature went to stream2 (ev_wfeat pending)
-    // The one-shot call's K5 plan (a memset of the workspace + four to six tables of a few KB, each a ~5 us blit kernel) goes up on
-    // a stream of its own beside K1-K4; the main stream waits for ev_plan in front of K5.  (In the main stream the copies sat
+    // The one-shot call's K5 plan (the workspace's clear where it is due + the tables, one image of a few KB) goes up on
+    // a stream of its own beside K1-K4; the main stream waits for ev_plan_up in front of K5.  (In the main stream the copies sat
     // between k_feature and k_lsweep: 25 us of the call at the headline, rocprofv3 --memory-copy-trace.)
     hipStream_t stream_up = nullptr;
-    hipEvent_t ev_plan = nullptr;
     hipStream_t plan_stream = nullptr;    // where upload_plan puts its copies (stream, or stream_up in the one-shot call)
-    void* hPlan = nullptr; size_t hPlanCap = 0;   // pinned staging image of the plan tables
-    hipEvent_t ev_plan_up = nullptr; bool plan_staged = false;   // ... its copies are through
+    // pinned staging images of the plan tables, used in turn: an upload waits for the copy of the upload before the last, not for
+    // its predecessor's.  ev_plan_up[i]: image i's copy is through (the main stream waits for it in front of K5)
+    void* hPlan[2] = {nullptr, nullptr}; size_t hPlanCap[2] = {0, 0};
+    hipEvent_t ev_plan_up[2] = {nullptr, nullptr}; bool plan_staged[2] = {false, false};
+    int plan_img = 0;                     // the image of the last upload
     // The one-shot call's P and poses go up on stream_up too, beside the tracks; the main stream waits for ev_state in front of K1.
     hipEvent_t ev_state = nullptr;
     bool state_pending = false;           // ev_state recorded, the main stream has not been told to wait for it yet
@@ -575,6 +605,19 @@ int ensure(msckf_ctx* c, Buf& b, size_t bytes, bool zero = false) {
 
 template <typename Tp>
 Tp* ptr(const Buf& b) { return reinterpret_cast<Tp*>(b.p); }
+
+// The R workspace holds `need` bytes; a new allocation gets `want`, and with MSCKF_DEBUG_POISON it starts as NaN (on `st`, where
+// the caller's clear follows).  Whatever the old one's head held is gone with it.
+int workspace_room(msckf_ctx* c, size_t need, size_t want, hipStream_t st) {
+    if (c->dRbuf.bytes >= need) return MSCKF_OK;
+    if (c->dRbuf.p) HIPCHK(c, hipFree(c->dRbuf.p));
+    c->dRbuf.p = nullptr; c->dRbuf.bytes = 0;
+    c->ws_key_valid = false;
+    HIPCHK(c, hipMalloc(&c->dRbuf.p, want));
+    c->dRbuf.bytes = want;
+    if (c->ws_poison) HIPCHK(c, hipMemsetAsync(c->dRbuf.p, 0xFF, want, st));
+    return MSCKF_OK;
+}
 
 // clone poses: host mirror -> pinned arena image -> HBM, one copy
 int upload_poses(msckf_ctx* c, hipStream_t st = nullptr) {
@@ -878,6 +921,42 @@ void sweep_publish_table(std::vector<int>& tab, size_t off, int nsteps, int wtot
     }
 }
 
+// Schedule and tables of the node with folds [begin, end): t0 of the folds and *nsteps are set, the returned entry holds the flush
+// table (every row final at the head of which macro step) and, with `gate`, the gate table behind it.  From the memo where the
+// same folds were seen before.
+int sweep_tables(msckf_ctx* c, std::vector<SweepFold>& folds, int begin, int end, int wtot, int nf, bool adopt, bool gate, int* nsteps) {
+    SweepMemo& m = c->memo;
+    std::vector<int>& key = m.key;
+    key.clear();
+    key.push_back(wtot); key.push_back(nf); key.push_back(adopt ? 1 : 0); key.push_back(gate ? 1 : 0);
+    for (int g = begin; g < end; ++g) {
+        const SweepFold& f = folds[g];
+        key.push_back(f.off); key.push_back(f.w); key.push_back(f.ew); key.push_back(f.prod); key.push_back(f.ld);
+    }
+    for (size_t i = 0; i < m.e.size(); ++i) {
+        const SweepTables& t = m.e[i];
+        if (t.key == key) {
+            for (int g = begin; g < end; ++g) folds[g].t0 = t.t0[g - begin];
+            *nsteps = t.nsteps;
+            return (int)i;
+        }
+    }
+    int slot;
+    if ((int)m.e.size() < SweepMemo::CAP) { slot = (int)m.e.size(); m.e.emplace_back(); }
+    else { slot = m.next; m.next = (m.next + 1) % SweepMemo::CAP; }
+    SweepTables& t = m.e[slot];
+    m.at[slot] = -1;
+    t.key = key;
+    sweep_schedule(folds, begin, end, &t.nsteps, nf, adopt);
+    t.t0.clear();
+    for (int g = begin; g < end; ++g) t.t0.push_back(folds[g].t0);
+    t.tab.clear();
+    sweep_flush_table(folds, begin, end, t.nsteps, wtot, 1 << 29, t.tab);
+    t.n_gate = gate ? sweep_gate_table(folds, begin, end, t.nsteps, nf, t.tab) : -1;
+    *nsteps = t.nsteps;
+    return slot;
+}
+
 bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<int>& fmax,
                      const std::vector<int>& view_sorted, const std::vector<unsigned char>* valid, const std::vector<Run>& runs) {
     const int N = c->N, dc = 6 * N;
@@ -927,19 +1006,29 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
                            6 * max_span + 1 <= 64 && c->leaf_nf == SWEEP_NW && !c->leaf_tall;
     c->leaf_ld64 = leaf_cand;
     c->leaf_fused = false;
-    std::vector<int> fold_leaf;                                           // per sweep fold: the leaf node it takes, -1: none
+    // (the planner's lists keep their capacity from call to call: a plan miss allocates nothing once the window's shape was seen)
+    static thread_local std::vector<int> fold_leaf;                       // per sweep fold: the leaf node it takes, -1: none
+    fold_leaf.clear();
+    if (!c->plan_memo) c->memo.e.clear();                                 // (tables shared within this plan only)
+    std::fill(c->memo.at, c->memo.at + SweepMemo::CAP, -1);
     c->nodes.clear(); c->levels.clear(); c->snodes.clear(); c->sfolds.clear();
     c->sweep_levels.clear(); c->n_group_merges = 0;
     // group exchange: the record [N flags | accepted count | gate bytes (msckf_set_exchange_mask) | N slots of XCHG_SLOT doubles]
     // heads the workspace; the triangle of
     // group s (fixed window of min(10, N - s) slots, so its shape depends on (N, s) only) is produced in slot s
     const bool xchg = c->xchg;
-    size_t off = xchg ? rec_head(c) + (size_t)N * XCHG_SLOT + rec_rem_doubles(c) : 0;
+    // k_sweep form, no export record, no split long tracks: the root block and the zero words head the workspace, where they
+    // stay from plan to plan (msckf_ctx::ws_head); the leaves' and the merges' blocks, which move with the leaf counts, behind them
+    const bool head = mode == 0 && !xchg && !c->split_on && runs.size() == 1;
+    const size_t head_zero = ((size_t)dc * (dc + 1) + 15) & ~(size_t)15;
+    size_t off = xchg ? rec_head(c) + (size_t)N * XCHG_SLOT + rec_rem_doubles(c) : head ? head_zero + 16 : 0;
     if (xchg) c->h_xflags.assign(N, 0.0);
     struct Tri { long long src; int lo, w; int lvl = -1, idx = -1, ld = 0, leaf = -1; };   // (lvl, idx): the merge node that writes it, if one does; ld: its row stride (0: w + 1); leaf: the leaf node that does
     const int merge_ld = (c->stream_enabled && mode == 0 && !xchg) ? 64 : 0;      // merge outputs with whole cache lines per row (streamable, k_sweep.h)
-    std::vector<Tri> group_tri;                                           // one triangle per group, by first slot
-    std::vector<std::vector<SweepNode>> merge_levels;                     // [level] -> nodes of every group at that depth
+    static thread_local std::vector<Tri> group_tri, leaves, tris, nxt;    // group_tri: one triangle per group, by first slot
+    static thread_local std::vector<std::vector<SweepNode>> merge_levels; // [level] -> nodes of every group at that depth
+    group_tri.clear();
+    int n_mlv = 0;                                                        // levels of this plan (merge_levels keeps the lists of earlier ones)
     // every run is sorted by (first slot, last slot) on its own (the tracks; the narrow blocks of split long tracks): the
     // groups are walked over all runs together, a leaf takes entries of ONE run
     std::vector<int> cur(runs.size());
@@ -952,7 +1041,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
         }
         if (s == (1 << 30)) break;
         // leaves of this group
-        std::vector<Tri> leaves;
+        leaves.clear();
         for (size_t r = 0; r < runs.size(); ++r) {
         int& f = cur[r];
         const int F = runs[r].e;
@@ -983,7 +1072,8 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
         }
         // merge levels of this group: one k_sweep node folds up to 2 * SWEEP_NW triangles (two rounds of the
         // fold slots); larger groups first reduce chunks of SWEEP_NW triangles in parallel workgroups
-        std::vector<Tri> cur = leaves;
+        std::vector<Tri>& cur = tris;
+        cur = leaves;
         const long long xdest = xchg ? (long long)(rec_head(c) + (size_t)s * XCHG_SLOT) : -1;
         auto merge_node = [&](size_t b, size_t e, int level, long long dest = -1) -> Tri {
             SweepNode m{};
@@ -1002,12 +1092,13 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
             if (dest >= 0) m.out_off = dest;
             else { m.ldo = merge_ld; m.out_off = (long long)off; off += (size_t)wtot * (merge_ld ? merge_ld : wtot + 1); }
             if ((int)merge_levels.size() <= level) merge_levels.resize(level + 1);
+            while (n_mlv <= level) merge_levels[n_mlv++].clear();
             merge_levels[level].push_back(m);
             return Tri{m.out_off, s, wtot, level, (int)merge_levels[level].size() - 1, m.ldo};
         };
         int level = 0;
         while (cur.size() > (size_t)(2 * SWEEP_NW)) {
-            std::vector<Tri> nxt;
+            nxt.clear();
             for (size_t b = 0; b < cur.size(); b += SWEEP_NW) {
                 const size_t e = std::min(cur.size(), b + SWEEP_NW);
                 nxt.push_back(e - b == 1 ? cur[b] : merge_node(b, e, level));
@@ -1036,7 +1127,8 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
     if (c->n_leaves > 0) c->levels.push_back({0, c->n_leaves});
     c->sweep_levels.clear();
     c->sweep_level_nf.clear();
-    for (auto& lv : merge_levels) {
+    for (int li = 0; li < n_mlv; ++li) {
+        auto& lv = merge_levels[li];
         // a level is one launch: twelve fold slots when a node has more triangles than eight slots take in one round
         // (groups of 9 - 16 leaf triangles at >= 10000 features: 60 + 9 macro steps instead of two rounds of 61)
         int most = 0;
@@ -1052,7 +1144,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
     // slots) and its triangles are streamed to the root
     c->root_streamed = false; c->stream_level = -1; c->h_mflush.clear();
     {
-        const int last = (int)merge_levels.size() - 1;
+        const int last = n_mlv - 1;
         // (every workgroup of that launch -- root, strips, merge nodes -- holds a CU of its own while it waits for the others:
         //  at most half of the device, so that a partitioned GPU or a kernel on another stream cannot keep a producer out)
         if (c->stream_enabled && mode == 0 && !xchg && last >= 0 && c->sweep_level_nf[last] <= SWEEP_NW_MID && (int)merge_levels[last].size() <= 64 &&
@@ -1086,6 +1178,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
             }
         }
     }
+    int root_tab = -1;                                                    // the root's entry of the memo
     if (!group_tri.empty()) {
         SweepNode r{};
         r.fold_begin = (int)c->sfolds.size();
@@ -1098,19 +1191,22 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
         }
         r.fold_end = (int)c->sfolds.size();
         r.wtot = dc;
-        sweep_schedule(c->sfolds, r.fold_begin, r.fold_end, &r.nsteps, SWEEP_NW, !c->root_streamed);
-        r.out_off = (long long)off;
-        c->root_off = off;
-        off += (size_t)dc * (dc + 1);
+        // (k_sweep form: the schedule comes with the flush table and, streamed, the gate table -- all three from the memo)
+        if (mode == 0) root_tab = sweep_tables(c, c->sfolds, r.fold_begin, r.fold_end, dc, SWEEP_NW, !c->root_streamed, c->root_streamed, &r.nsteps);
+        else sweep_schedule(c->sfolds, r.fold_begin, r.fold_end, &r.nsteps, SWEEP_NW, !c->root_streamed);
+        c->root_off = head ? 0 : off;
+        r.out_off = (long long)c->root_off;
+        if (!head) off += (size_t)dc * (dc + 1);
         c->snodes.push_back(r);
         c->root = 0;
     } else {
         c->root = -1;
         c->root_off = 0;
     }
-    c->zero_off = off;
-    off += 16;
+    if (head) c->zero_off = head_zero;
+    else { c->zero_off = off; off += 16; }
     c->rbuf_doubles = off;
+    c->ws_head = head;
     c->xchg_planned = xchg;
     c->h_flush.clear(); c->h_flush_off.clear();
     c->h_root_flush.clear();
@@ -1119,29 +1215,27 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
         // the root's rows become final one by one as the sweep passes them: K6-K7 (k_gstream.h) follows them block by block
         const SweepNode& rn = c->snodes.back();
         for (int g = rn.fold_begin; g < rn.fold_end; ++g) c->root_band = std::max(c->root_band, c->sfolds[g].ew);
-        if (mode == 0) sweep_flush_table(c->sfolds, rn.fold_begin, rn.fold_end, rn.nsteps, rn.wtot, 1 << 29, c->h_root_flush);
         c->root_n_gate = -1;
+        if (mode == 0) {
+            const SweepTables& rt = c->memo.e[root_tab];
+            c->h_root_flush.assign(rt.tab.begin(), rt.tab.end());
+            c->root_n_gate = rt.n_gate;
+        }
         if (c->root_streamed) {
-            c->root_n_gate = sweep_gate_table(c->sfolds, rn.fold_begin, rn.fold_end, rn.nsteps, SWEEP_NW, c->h_root_flush);
             const auto& lv = c->sweep_levels[c->stream_level];
             c->h_mflush.assign(lv.second, 0);
             // (nodes with the same folds -- the same number of triangles of the same widths: most of them -- share one table)
             // (with the leaves in the launch each table carries the node's gate table and step-0 requirements behind it)
-            std::vector<std::pair<std::vector<int>, std::pair<int, int>>> seen_shapes;
+            const int nf_lv = c->leaf_fused ? SWEEP_NW : c->sweep_level_nf[c->stream_level];
             for (int i = 0; i < lv.second; ++i) {
                 SweepNode& m = c->snodes[lv.first + i];
-                std::vector<int> shape{m.wtot, m.nsteps};
-                for (int g = m.fold_begin; g < m.fold_end; ++g) { shape.push_back(c->sfolds[g].w); shape.push_back(c->sfolds[g].ew); shape.push_back(c->sfolds[g].t0); shape.push_back(c->sfolds[g].off); shape.push_back(c->sfolds[g].prod); }
-                int at = -1, ng = -1;
-                for (const auto& sh : seen_shapes) if (sh.first == shape) { at = sh.second.first; ng = sh.second.second; break; }
-                if (at < 0) {
-                    at = (int)c->h_mflush.size() - lv.second;
-                    sweep_flush_table(c->sfolds, m.fold_begin, m.fold_end, m.nsteps, m.wtot, 1 << 29, c->h_mflush);
-                    if (c->leaf_fused) ng = sweep_gate_table(c->sfolds, m.fold_begin, m.fold_end, m.nsteps, SWEEP_NW, c->h_mflush);
-                    seen_shapes.push_back({std::move(shape), {at, ng}});
+                const int slot = sweep_tables(c, c->sfolds, m.fold_begin, m.fold_end, m.wtot, nf_lv, !c->leaf_fused, c->leaf_fused, &m.nsteps);
+                if (c->memo.at[slot] < 0) {
+                    c->memo.at[slot] = (int)c->h_mflush.size() - lv.second;
+                    c->h_mflush.insert(c->h_mflush.end(), c->memo.e[slot].tab.begin(), c->memo.e[slot].tab.end());
                 }
-                c->h_mflush[i] = at;
-                m.n_gate = ng;
+                c->h_mflush[i] = c->memo.at[slot];
+                m.n_gate = c->memo.e[slot].n_gate;
             }
             c->mflush_at = (int)c->h_root_flush.size();         // (one upload: the merge nodes' tables ride behind the root's)
             c->h_root_flush.insert(c->h_root_flush.end(), c->h_mflush.begin(), c->h_mflush.end());
@@ -1164,6 +1258,7 @@ void plan_batch(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
                 const std::vector<int>& view_sorted, const std::vector<unsigned char>* valid_in = nullptr) {
     c->xchg_planned = false;
     c->wide_active = false;
+    c->ws_head = false;
     c->rnodes.clear(); c->rlevels.clear(); c->rroot = -1; c->rroot_off = 0; c->rtops.clear(); c->rtop_rows = 0;
     const int F = c->F, Fs = c->Fs;
     // a block is as valid as the track it was split off
@@ -1176,7 +1271,7 @@ void plan_batch(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
         valid = &vfull;
     }
     auto tree_only = [&](const std::vector<Run>& runs) {
-        c->band_plan = false;
+        c->band_plan = false; c->ws_head = false;
         c->snodes.clear(); c->sfolds.clear(); c->sweep_levels.clear(); c->n_group_merges = 0;
         c->h_root_flush.clear();
         size_t off_end = 0;
@@ -1387,8 +1482,8 @@ int upload_plan(msckf_ctx* c) {
     hipStream_t ps = c->plan_stream ? c->plan_stream : c->stream;
     // The tables (leaf nodes, sweep nodes and folds, the flush / gate tables) go up as ONE image: pinned staging -> one arena in
     // HBM, the buffers the launches name are views into it.  (As four to six copies they cost the host ~5 us each inside the
-    // window of K1-K4, and the device a blit kernel each.)  The staging image is reused: wait for the previous plan's copy
-    // first (an event that has long passed by then).
+    // window of K1-K4, and the device a blit kernel each.)  Two staging images take turns: the one written here was last read
+    // by the copy of the upload before the last.
     size_t need = 0;
     auto room = [&](size_t bytes) { const size_t o = need; need += (std::max<size_t>(bytes, 64) + 255) & ~(size_t)255; return o; };
     const size_t b_nodes = c->nodes.size() * sizeof(FoldNode), b_sn = c->snodes.size() * sizeof(SweepNode), b_sf = c->sfolds.size() * sizeof(SweepFold);
@@ -1396,12 +1491,13 @@ int upload_plan(msckf_ctx* c) {
     const size_t b_rn = c->rnodes.size() * sizeof(FoldNode);
     const size_t o_nodes = room(b_nodes), o_sn = room(b_sn), o_sf = room(b_sf), o_rf = room(b_rf), o_fl = room(b_fl), o_fo = room(b_fo);
     const size_t o_rn = room(b_rn);
-    if (c->plan_staged) { HIPCHK(c, hipEventSynchronize(c->ev_plan_up)); c->plan_staged = false; }
-    if (c->hPlanCap < need) {
-        if (c->hPlan) HIPCHK(c, hipHostFree(c->hPlan));
-        c->hPlan = nullptr; c->hPlanCap = 0;
-        HIPCHK(c, hipHostMalloc(&c->hPlan, 2 * need + 4096));
-        c->hPlanCap = 2 * need + 4096;
+    const int img = c->plan_img ^= 1;
+    if (c->plan_staged[img]) { HIPCHK(c, hipEventSynchronize(c->ev_plan_up[img])); c->plan_staged[img] = false; }
+    if (c->hPlanCap[img] < need) {
+        if (c->hPlan[img]) HIPCHK(c, hipHostFree(c->hPlan[img]));
+        c->hPlan[img] = nullptr; c->hPlanCap[img] = 0;
+        HIPCHK(c, hipHostMalloc(&c->hPlan[img], 2 * need + 4096));
+        c->hPlanCap[img] = 2 * need + 4096;
     }
     // (buffers of their own from a merge plan that outgrew the arena: released before they become views again)
     for (Buf* bb : {&c->dNodes, &c->dSweepNodes, &c->dSweepFolds, &c->dRootFlush, &c->dFlush, &c->dFlushOff, &c->dRNodes})
@@ -1410,7 +1506,7 @@ int upload_plan(msckf_ctx* c) {
         HIPCHK(c, hipStreamSynchronize(c->stream));        // (kernels of an earlier run may still read the old arena)
         if (int rc = ensure(c, c->dPlanArena, 2 * need)) return rc;
     }
-    char* hp = static_cast<char*>(c->hPlan);
+    char* hp = static_cast<char*>(c->hPlan[img]);
     if (b_nodes) std::memcpy(hp + o_nodes, c->nodes.data(), b_nodes);
     if (b_sn) std::memcpy(hp + o_sn, c->snodes.data(), b_sn);
     if (b_sf) std::memcpy(hp + o_sf, c->sfolds.data(), b_sf);
@@ -1429,8 +1525,8 @@ int upload_plan(msckf_ctx* c) {
     c->x_plan_valid = false;               // the sweep tables are rewritten: a cached merge plan behind them is gone
     if (c->xchg_planned)                   // (behind the workspace memset of set_features / replan, same stream)
         HIPCHK(c, hipMemcpyAsync(c->dRbuf.p, c->h_xflags.data(), c->h_xflags.size() * 8, hipMemcpyHostToDevice, ps));
-    HIPCHK(c, hipEventRecord(c->ev_plan_up, ps));
-    c->plan_staged = true;
+    HIPCHK(c, hipEventRecord(c->ev_plan_up[img], ps));
+    c->plan_staged[img] = true;
     return MSCKF_OK;
 }
 
@@ -2003,7 +2099,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     if (chain) {
         hipStream_t rs = c->wide_on_stream2 ? c->stream2 : c->stream;
         // (the tree reads the plan's tables and writes the workspace: behind their upload / memset, which the main stream is
-        //  behind by now -- ev_plan, set_features)
+        //  behind by now -- ev_plan_up, set_features)
         if (c->wide_on_stream2) { HIPCHK(c, hipEventRecord(c->ev_fork, c->stream)); HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0)); }
         if ((rc = launch_fold_levels(c, c->rlevels, c->rnodes, rs, ptr<FoldNode>(c->dRNodes))) != MSCKF_OK) return rc;
         if (!c->rtops.empty() && (rc = launch_tri_gather(c, rs)) != MSCKF_OK) return rc;
@@ -2283,13 +2379,14 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     CK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming), "hipEventCreate");
     CK(hipEventCreateWithFlags(&c->ev_wfeat, hipEventDisableTiming), "hipEventCreate");
     CK(hipEventCreateWithFlags(&c->ev_rem, hipEventDisableTiming), "hipEventCreate");
-    CK(hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming), "hipEventCreate");
-    CK(hipEventCreateWithFlags(&c->ev_plan_up, hipEventDisableTiming), "hipEventCreate");
+    for (auto& e : c->ev_plan_up) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
     CK(hipEventCreateWithFlags(&c->ev_state, hipEventDisableTiming), "hipEventCreate");
     CK(hipEventCreateWithFlags(&c->ev_gate, hipEventDisableTiming), "hipEventCreate");
     if (const char* e = std::getenv("MSCKF_DIRECT_RESULT")) c->direct_enabled = std::atoi(e) != 0;
     if (const char* e = std::getenv("MSCKF_ROOT_STREAM")) c->stream_enabled = std::atoi(e) != 0;
     if (const char* e = std::getenv("MSCKF_LEAF_STREAM")) c->leaf_stream_enabled = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MSCKF_DEBUG_POISON")) c->ws_poison = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MSCKF_PLAN_MEMO")) c->plan_memo = std::atoi(e) != 0;
     auto lds_attr = [&](const void* f, int bytes, const char* what) {
         CK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), what);
     };
@@ -2454,9 +2551,8 @@ void msckf_destroy(msckf_ctx* c) {
     if (c->ev_wfeat) (void)hipEventDestroy(c->ev_wfeat);
     if (c->ev_rem) (void)hipEventDestroy(c->ev_rem);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->ev_plan) (void)hipEventDestroy(c->ev_plan);
-    if (c->ev_plan_up) (void)hipEventDestroy(c->ev_plan_up);
-    if (c->hPlan) (void)hipHostFree(c->hPlan);
+    for (hipEvent_t e : c->ev_plan_up) if (e) (void)hipEventDestroy(e);
+    for (void* h : c->hPlan) if (h) (void)hipHostFree(h);
     if (c->ev_state) (void)hipEventDestroy(c->ev_state);
     if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
     for (PinStage* ps : {&c->trk_obs_stage, &c->trk_load_stage, &c->trk_frame_stage, &c->trk_match_stage, &c->trk_desc_stage}) {
@@ -2541,12 +2637,8 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
             // a shard without tracks still takes part in the gather: an empty record (no flag, count 0, no gate byte)
             // heads the workspace; the triangles behind it are never read (the merging rank goes by the flags)
             const size_t need = (rec_head(c) + (size_t)N * rec_slot(c) + rec_rem_doubles(c) + 16) * 8;
-            if (c->dRbuf.bytes < need) {
-                if (c->dRbuf.p) HIPCHK(c, hipFree(c->dRbuf.p));
-                c->dRbuf.p = nullptr; c->dRbuf.bytes = 0;
-                HIPCHK(c, hipMalloc(&c->dRbuf.p, need));
-                c->dRbuf.bytes = need;
-            }
+            if (int rcw = workspace_room(c, need, need, c->stream)) return rcw;
+            c->ws_key_valid = false;
             HIPCHK(c, hipMemsetAsync(c->dRbuf.p, 0, rec_head(c) * 8, c->stream));
             if (c->xsplit_rows > 0) HIPCHK(c, hipMemsetAsync(ptr<double>(c->dRbuf) + rec_rem_off(c), 0, 8, c->stream));   // no remainder row
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2877,27 +2969,26 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     const double t3 = now_us();
     c->us_host_prep = (float)((t1 - t0) + (t3 - t2));
     if (!plan_hit) {
-        // the R workspace is zero-initialised once: entries below a block's diagonal are never written
         const size_t need = (c->rbuf_doubles + 16) * 8;
-        if (c->dRbuf.bytes < need) {
-            if (c->dRbuf.p) HIPCHK(c, hipFree(c->dRbuf.p));
-            c->dRbuf.p = nullptr; c->dRbuf.bytes = 0;
-            const size_t want = need + need / 2;
-            HIPCHK(c, hipMalloc(&c->dRbuf.p, want));
-            c->dRbuf.bytes = want;
-        }
         // (on the side stream unless a pipeline nobody waited for may still be reading the workspace or the tables)
         const bool side = c->oneshot || !c->run_pending;
         c->plan_stream = side ? c->stream_up : c->stream;
-        HIPCHK(c, hipMemsetAsync(c->dRbuf.p, 0, need, c->plan_stream));
+        if (int rcw = workspace_room(c, need, need + need / 2, c->plan_stream)) { c->plan_stream = nullptr; return rcw; }
+        // The R workspace is zero-initialised: entries below a block's diagonal are never written.  A plan with the root block and
+        // the zero words at the head (ws_head) reads nothing else that it has not written in the same run, and the head lies where
+        // the last such plan at this dc left it: cleared once, nothing to clear on this miss.
+        const bool keep = c->ws_head && c->ws_key_valid && c->ws_key_p == c->dRbuf.p && c->ws_key_dc == c->dc;
+        if (!keep) HIPCHK(c, hipMemsetAsync(c->dRbuf.p, 0, need, c->plan_stream));
+        else if (c->ws_poison) {
+            const size_t head = (c->zero_off + 16) * 8;
+            HIPCHK(c, hipMemsetAsync(static_cast<char*>(c->dRbuf.p) + head, 0xFF, need - head, c->plan_stream));
+        }
+        c->ws_key_valid = c->ws_head; c->ws_key_p = c->dRbuf.p; c->ws_key_dc = c->dc;
         c->plan_valid = false;
         const int rcp = upload_plan(c);
-        if (side) {
-            HIPCHK(c, hipEventRecord(c->ev_plan, c->stream_up));
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_plan, 0));
-        }
         c->plan_stream = nullptr;
         if (rcp) return rcp;
+        if (side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_plan_up[c->plan_img], 0));
         c->plan_fmin = h_fmin; c->plan_fmax = h_fmax;
         c->plan_valid = true;
         c->plan_no_wide = false;
@@ -2937,12 +3028,8 @@ static int replan_current(msckf_ctx* c, bool one_plan) {
     c->plan_no_wide = true;                // (not a plan the cache may hand to the next batch)
     c->gather_off = c->rbuf_doubles;
     const size_t need = (c->rbuf_doubles + 16) * 8;
-    if (c->dRbuf.bytes < need) {
-        if (c->dRbuf.p) HIPCHK(c, hipFree(c->dRbuf.p));
-        c->dRbuf.p = nullptr; c->dRbuf.bytes = 0;
-        HIPCHK(c, hipMalloc(&c->dRbuf.p, need + need / 2));
-        c->dRbuf.bytes = need + need / 2;
-    }
+    if (int rcw = workspace_room(c, need, need + need / 2, c->stream)) return rcw;
+    c->ws_key_valid = false;               // (a re-plan is no plan miss: the next miss clears again)
     HIPCHK(c, hipMemsetAsync(c->dRbuf.p, 0, need, c->stream));
     return upload_plan(c);
 }
@@ -3287,12 +3374,8 @@ int msckf_replan(msckf_ctx* c) {
     // the blocks moved inside the R workspace: entries below their diagonals must read as zero again
     {
         const size_t need = (c->rbuf_doubles + 16) * 8;
-        if (c->dRbuf.bytes < need) {
-            if (c->dRbuf.p) HIPCHK(c, hipFree(c->dRbuf.p));
-            c->dRbuf.p = nullptr; c->dRbuf.bytes = 0;
-            HIPCHK(c, hipMalloc(&c->dRbuf.p, need + need / 2));
-            c->dRbuf.bytes = need + need / 2;
-        }
+        if (int rcw = workspace_room(c, need, need + need / 2, c->stream)) return rcw;
+        c->ws_key_valid = false;
         HIPCHK(c, hipMemsetAsync(c->dRbuf.p, 0, need, c->stream));
     }
     if (int rcp = upload_plan(c)) return rcp;
@@ -4020,12 +4103,14 @@ int grow_workspace(msckf_ctx* c, size_t need) {
         HIPCHK(c, hipFree(c->dRbuf.p));
     }
     c->dRbuf.p = np; c->dRbuf.bytes = need;
+    c->ws_key_valid = false;
     c->x_plan_valid = false;              // (a cached merge plan names offsets from the old base)
     return MSCKF_OK;
 }
 // A merge has its own sources of rows, whatever the rank's own last batch looked like, and status words 1 and 4 are its own: nothing
 // an earlier batch or merge left there may be read as its outcome
 int begin_merge(msckf_ctx* c) {
+    c->ws_key_valid = false;               // (the merge works in the workspace too: the next plan miss clears it)
     HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 1, 0, 4, c->stream));
     HIPCHK(c, hipMemsetAsync(ptr<int>(c->dStatus) + 4, 0, 4, c->stream));
     return MSCKF_OK;

@@ -41,33 +41,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wave_ops.h"
+#include "sweep_plan.h"     // SweepFold, SweepNode, SWEEP_MAX_W and the host's schedule / table functions
 
 namespace msckf {
-
-struct SweepFold {
-    long long src_off;   // offset (doubles) of the source block in rbuf: row-major w x (w+1), upper triangular
-    int off;             // first column of the source window, local to the node
-    int w;               // rows / columns of the source triangle (<= SWEEP_MAX_W)
-    int ew;              // tile width: columns [off, off+ew) may fill in (w <= ew <= SWEEP_MAX_W)
-    int t0;              // macro step of the fold's first column
-    int prod;            // 0, or 1 + index of the progress word of the node that is still WRITING the source block in the same
-                         // launch (k_root_gain's merge workgroups): the flusher lets a macro step start only when the rows its
-                         // folds fetch in it are published (host table, sweep_gate_table)
-    int ld;              // doubles per row of the source block (0: w + 1).  A streamed block has whole cache lines per row (64):
-                         // a line fetched for a published row must not hold part of a row that is not final yet
-};
-
-struct SweepNode {
-    int fold_begin, fold_end;   // folds [begin, end); a first fold with t0 == 0 is adopted (copied into R), the others
-                                // run on fold slot (i - first scheduled) % NF
-    int wtot;                   // columns of the node's R
-    int nsteps;                 // macro steps
-    long long out_off;          // output block in rbuf: row-major wtot x (wtot+1), or wtot x ldo
-    int ldo;                    // doubles per row of the output block (0: wtot + 1)
-    int prod_base;              // streamed sources: SweepFold::prod counts from progress word src_progress[prod_base]
-    int n_gate;                 // ... the step-0 requirements behind this node's own gate table (SweepArgs::gate_per_node)
-    int pad;
-};
 
 struct SweepArgs {
     const SweepNode* nodes;
@@ -96,7 +72,6 @@ struct SweepArgs {
                                 // workgroups, gated on the leaves): SweepNode::n_gate replaces n_gate, SweepNode::prod_base applies
 };
 
-constexpr int SWEEP_MAX_W = 60;        // widest source / envelope (local column 63 holds the rhs)
 constexpr int SWEEP_RS = 64;           // doubles per R row in LDS: entry (c, col) at [c][col - c], rhs at [c][63]
 constexpr double SWEEP_TINY = 1e-290;  // |column|^2 under this is treated as an exact zero column
 constexpr long long SWEEP_TIMEOUT_TICKS = 50000000;   // 0.5 s of the 100 MHz wall clock: a streamed source that never arrives

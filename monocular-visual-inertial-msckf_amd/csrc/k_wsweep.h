@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "k_sweep.h"
+#include "sweep_plan.h"     // WS_PUB_LAG, sweep_flush_table, sweep_publish_table
 
 namespace msckf {
 
@@ -35,7 +36,6 @@ struct WSweepArgs {
     long long* tstamp;          // optional: [0] start, [1] last row published (10 ns wall-clock ticks)
 };
 
-constexpr int WS_PUB_LAG = 4;             // steps between a row's store and the wait for it (the count goes out one step later)
 template <int CS> struct WSweepGeom {
     static constexpr int W = 16 * CS;          // tile columns = LDS row stride
     static constexpr int MAX_W = W - 6;        // widest source / envelope

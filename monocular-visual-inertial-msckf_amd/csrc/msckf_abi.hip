@@ -285,24 +285,6 @@ struct RunRecord {
 
 }  // namespace
 
-// A sweep node's schedule and tables depend on its folds' shapes, not on where its sources lie or how many tracks they hold:
-// a window's group shape repeats from batch to batch, and most merge nodes of one plan share a shape.  Kept by the exact inputs
-// (key: wtot, fold slots, adopted, gate table wanted, then off, w, ew, prod, ld of every fold), so a hit IS the table a rebuild gives.
-struct SweepTables {
-    std::vector<int> key;
-    std::vector<int> t0;                  // SweepFold::t0 of the folds (sweep_schedule)
-    int nsteps = 0;
-    std::vector<int> tab;                 // sweep_flush_table, then sweep_gate_table where the key asks for it
-    int n_gate = -1;                      // ... its step-0 requirements; -1: no gate table
-};
-struct SweepMemo {
-    static constexpr int CAP = 64;
-    std::vector<SweepTables> e;           // up to CAP, the oldest replaced first
-    int next = 0;
-    int at[CAP];                          // where the entry's table sits in the plan being built, -1: not in it yet
-    std::vector<int> key;                 // (scratch)
-};
-
 struct msckf_ctx {
     msckf_config cfg{};
     int device = 0;
@@ -423,13 +405,12 @@ struct msckf_ctx {
     HostPool* pool = nullptr;             // host worker threads for the pack loops (CPU work only)
     // K6-K7 beside the root sweep (k_gstream.h, k_root_gain): the sequential block update polls the rows the sweep's flusher publishes
     Buf dGsEx, dGsFlag, dGsProg;          // exchange tiles [nb][ns][256], their flags, the sweep's progress word
-    Buf dRootFlush, dXRootFlush;          // flush tables of the root sweeps (rows final at the head of every macro step): local plan, merge plan
-    std::vector<int> h_root_flush;        // ... of the local plan's root (band plan, k_sweep form)
-    std::vector<int> x_root_flush;        // ... of the merge plan's root (msckf_run_merge_groups)
+    Buf dRootFlush, dXRootFlush;          // the table images of the root sweeps' launches on the device: local plan, merge plan
+    RootTables plan_tabs, merge_tabs;     // ... on the host (sweep_root): of the local plan's root (band plan), of rank 0's merge plan (run_merge_groups)
     unsigned gs_epoch = 0;                // tag of the current launch pair in the progress word and the exchange flags
     bool gs_enabled = true;               // MSCKF_GAIN_STREAM=0: the round-3 K6-K7 (separate launches behind the root sweep)
     bool gs_overlap = true;               // MSCKF_GAIN_OVERLAP=0: k_gain_stream as a launch of its own behind the root sweep
-    int root_band = 0;                    // widest row of the root block in columns (the local plan's / the merge plan's)
+    int root_band = 0;                    // widest row of the root block in columns (band plan: plan_tabs.band; tree plan: dc)
     bool gs_stamp = false;                // msckf_run_timed: k_root_gain notes when its sweep ends and when its update ends
     // tracks that span more than WIDE_SPAN clone slots are sorted behind the others ([0, Fb) short, [Fb, F) long) and split
     int Fb = 0, Fw = 0, Fw1 = 0, Mmax_band = 0, Mmax_wide = 0, Mmax_w1 = 0;   // (Fw1 of the Fw wide tracks have <= 15 views)
@@ -499,13 +480,9 @@ struct msckf_ctx {
     const uint8_t* gate_mask_dst = nullptr;
     bool direct_enabled = true;
     // The last level of group merges inside k_root_gain's launch, the root taking their rows as they are published (k_gstream.h):
-    bool root_streamed = false;           // this plan's root folds name their producers (SweepFold::prod), first fold not adopted
+    // plan_tabs.streamed, the level's tables behind the root's in the image
     int stream_level = -1;                // index of that level in sweep_levels
-    std::vector<int> h_mflush;            // [n offsets | the nodes' flush tables]
-    int mflush_at = 0;                    // where h_mflush sits in the uploaded h_root_flush
-    bool x_streamed = false; int x_root_n_gate = -1, x_mflush_at = 0;   // the same for rank 0's merge plan (run_merge_groups)
-    int root_n_gate = -1;                 // step-0 requirements behind the root's flush + gate tables (sweep_gate_table), -1: no gate table
-    Buf dMFlush, dMProg;                  // ... on the device; the merge nodes' progress words (64), then the fused leaves' (LEAF_PROG_BASE)
+    Buf dMFlush, dMProg;                  // the merge nodes' progress words (64), then the fused leaves' (LEAF_PROG_BASE)
     bool stream_enabled = true;           // MSCKF_ROOT_STREAM=0: the level keeps its own launch
     // The leaves in the same launch as well (k_leaf_root_gain): their rows streamed to the merge nodes (one merge level, 60-column
     // leaves of eight fold slots, no split long tracks)
@@ -802,21 +779,7 @@ void build_tree(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
 // Returns false when the batch does not qualify (wide tracks, R band over the LDS budget): tree plan then.
 constexpr int SWEEP_NW_BIG = 12;                 // k_sweep group merges of more than SWEEP_NW + 1 triangles: twelve fold slots, one round
 constexpr int SWEEP_NW_MID = 11;                 // ... of up to 12 triangles: eleven, so that the level fits k_root_gain_m's launch (twelve wavefronts with the flusher)
-void sweep_schedule(std::vector<SweepFold>& folds, int begin, int end, int* nsteps, int nf = SWEEP_NW, bool adopt = true) {
-    int last = 0;
-    if (end > begin && adopt) folds[begin].t0 = 0;         // adopted: copied into the empty R, no elimination steps
-    const int first = adopt ? begin + 1 : begin;           // (not adopted: a streamed first triangle is folded like the others)
-    for (int g = first; g < end; ++g) {
-        int t0 = 1;                                        // step t0 - 1 publishes the fold's first column
-        if (g > first) t0 = folds[g - 1].t0 + (folds[g].off - folds[g - 1].off) + 1;
-        // (a fold runs one step per column of its ENVELOPE ew >= w: where R already reaches further right than the
-        //  source triangle, the tile's rows fill in there and the fill has to be eliminated as well)
-        if (g - first >= nf) t0 = std::max(t0, folds[g - nf].t0 + folds[g - nf].ew + 1);
-        folds[g].t0 = t0;
-        last = std::max(last, t0 + folds[g].ew);
-    }
-    *nsteps = last;
-}
+static_assert(SWEEP_PLAN_NF == SWEEP_NW, "sweep_schedule's default is the sweep kernels' slot count");
 
 // Which sweep kernel runs the group merges and the root of a batch of N clones whose longest track spans
 // `max_span` clone slots: 0 = k_sweep (tiles of 60 columns, the whole band R in LDS), 1 = k_wsweep<4> (the
@@ -836,126 +799,6 @@ int sweep_mode_for(const msckf_ctx* c, int N, int max_span) {
 // THE rule for the group exchange of the sharded band pipeline (msckf_band_rule exports it): the record
 // layout and the merging rank's sweeps are those of k_sweep.
 bool band_rule(const msckf_ctx* c, int N, int max_span) { return sweep_mode_for(c, N, max_span) >= 0; }
-
-// k_wsweep: rows of R no present or future fold step touches at the head of macro step t (the schedule is
-// static).  Entry t = lo | n << 16: rows [lo, lo + n) leave the ring at the head of step t; entry nsteps covers
-// the rest.  Returns false when some step would touch a row whose ring slot still holds an unflushed row.
-bool sweep_flush_table(const std::vector<SweepFold>& folds, int begin, int end, int nsteps, int wtot, int rc,
-                       std::vector<int>& tab) {
-    const int first = (end > begin && folds[begin].t0 == 0) ? begin + 1 : begin;   // an adopted triangle runs no step
-    int lprev = 0;
-    bool ok = true;
-    for (int t = 0; t <= nsteps; ++t) {
-        int L = wtot, H = -1;
-        if (t < nsteps) {
-            for (int g = first; g < end; ++g) {
-                const SweepFold& f = folds[g];
-                if (t >= f.t0 + f.ew) continue;                           // finished (one step per envelope column)
-                const int row = f.off + std::max(0, t - f.t0);            // its present (or first) pivot row
-                L = std::min(L, row);
-                if (t >= f.t0) H = std::max(H, row);
-            }
-        }
-        L = std::max(L, lprev);
-        if (H >= lprev + rc) ok = false;                                  // a touched row aliases one flushed in this step
-        if (t == 0 && first > begin && folds[begin].off + folds[begin].w > rc) ok = false;   // the adopted rows fit the ring
-        tab.push_back(lprev | ((L - lprev) << 16));
-        lprev = L;
-    }
-    return ok;
-}
-
-// Streamed sources of a node (SweepFold::prod, k_root_gain's merge workgroups): which rows of which producer the fold
-// wavefronts fetch at the head of which macro step -- k_sweep.h fetches rows [0, 8) of a fold's source before step 0 (the first
-// nf folds) or in chunk max((ew' - 1) / 8 - 1, 0) of the fold that has the slot before it, and rows [8 KK + 8, 8 KK + 16) at
-// the head of the fold's chunk KK.  Appended to `tab`: nsteps + 2 step entries (up to two requirements prod << 6 | rows, 12 bits
-// each; a third moves to an earlier step, which only asks for it sooner) | the requirements of step 0.  Returns their count.
-int sweep_gate_table(const std::vector<SweepFold>& folds, int begin, int end, int nsteps, int nf, std::vector<int>& tab) {
-    const int first = (end > begin && folds[begin].t0 == 0) ? begin + 1 : begin;
-    // (step, requirement) pairs, then a counting sort by step: no per-step containers on the one-shot call's host path
-    static thread_local std::vector<std::pair<int, int>> req;
-    req.clear();
-    for (int i = first; i < end; ++i) {
-        const SweepFold& f = folds[i];
-        if (f.prod <= 0) continue;
-        int step = 0;
-        if (i - first >= nf) { const SweepFold& q = folds[i - nf]; step = q.t0 + 8 * std::max((q.ew - 1) / 8 - 1, 0); }
-        req.push_back({std::min(step, nsteps), ((f.prod - 1) << 6) | std::min(f.w, 8)});
-        for (int kk = 0; kk < 8 && 8 * kk < f.ew; ++kk)
-            if (8 * kk + 8 < f.w) req.push_back({std::min(f.t0 + 8 * kk, nsteps), ((f.prod - 1) << 6) | std::min(f.w, 8 * kk + 16)});
-    }
-    std::sort(req.begin(), req.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) { return x.first > y.first; });   // latest step first
-    const size_t base = tab.size();
-    tab.resize(base + nsteps + 2, 0);
-    std::vector<int> step0;
-    int carry[64], ncarry = 0;                      // requirements pushed to an earlier step (a step takes two)
-    size_t k = 0;
-    for (int t = nsteps + 1; t >= 0; --t) {
-        int mine[2], n = 0;
-        auto take = [&](int r) { if (t == 0) step0.push_back(r); else if (n < 2) mine[n++] = r; else if (ncarry < 64) carry[ncarry++] = r; else step0.push_back(r); };
-        const int nc = ncarry; ncarry = 0;
-        int prev[64];
-        for (int j = 0; j < nc; ++j) prev[j] = carry[j];
-        for (int j = 0; j < nc; ++j) take(prev[j]);
-        while (k < req.size() && req[k].first == t) take(req[k++].second);
-        if (t > 0) tab[base + t] = (n > 0 ? mine[0] : 0) | (n > 1 ? mine[1] << 12 : 0);
-    }
-    tab.insert(tab.end(), step0.begin(), step0.end());
-    return (int)step0.size();
-}
-
-// k_wsweep with PUB: what wavefront 0 publishes at the head of macro step t -- the rows that were final WS_PUB_LAG + 1 steps
-// earlier, where that count passes a boundary of k_gstream.h's 16-row blocks (they end at rows = wtot mod 16); 0: nothing.
-// Appended behind the node's flush entries (tab[off .. off + nsteps]).
-void sweep_publish_table(std::vector<int>& tab, size_t off, int nsteps, int wtot) {
-    const int boff = (16 - (wtot & 15)) & 15;
-    int published = 0;
-    for (int t = 0; t <= nsteps; ++t) {
-        int pr = 0;
-        if (t > WS_PUB_LAG) {
-            const int e = tab[off + t - WS_PUB_LAG - 1];
-            const int rows = (e & 0xFFFF) + (e >> 16);
-            if (((rows + boff) >> 4) > ((published + boff) >> 4)) { pr = rows; published = rows; }
-        }
-        tab.push_back(pr);
-    }
-}
-
-// Schedule and tables of the node with folds [begin, end): t0 of the folds and *nsteps are set, the returned entry holds the flush
-// table (every row final at the head of which macro step) and, with `gate`, the gate table behind it.  From the memo where the
-// same folds were seen before.
-int sweep_tables(msckf_ctx* c, std::vector<SweepFold>& folds, int begin, int end, int wtot, int nf, bool adopt, bool gate, int* nsteps) {
-    SweepMemo& m = c->memo;
-    std::vector<int>& key = m.key;
-    key.clear();
-    key.push_back(wtot); key.push_back(nf); key.push_back(adopt ? 1 : 0); key.push_back(gate ? 1 : 0);
-    for (int g = begin; g < end; ++g) {
-        const SweepFold& f = folds[g];
-        key.push_back(f.off); key.push_back(f.w); key.push_back(f.ew); key.push_back(f.prod); key.push_back(f.ld);
-    }
-    for (size_t i = 0; i < m.e.size(); ++i) {
-        const SweepTables& t = m.e[i];
-        if (t.key == key) {
-            for (int g = begin; g < end; ++g) folds[g].t0 = t.t0[g - begin];
-            *nsteps = t.nsteps;
-            return (int)i;
-        }
-    }
-    int slot;
-    if ((int)m.e.size() < SweepMemo::CAP) { slot = (int)m.e.size(); m.e.emplace_back(); }
-    else { slot = m.next; m.next = (m.next + 1) % SweepMemo::CAP; }
-    SweepTables& t = m.e[slot];
-    m.at[slot] = -1;
-    t.key = key;
-    sweep_schedule(folds, begin, end, &t.nsteps, nf, adopt);
-    t.t0.clear();
-    for (int g = begin; g < end; ++g) t.t0.push_back(folds[g].t0);
-    t.tab.clear();
-    sweep_flush_table(folds, begin, end, t.nsteps, wtot, 1 << 29, t.tab);
-    t.n_gate = gate ? sweep_gate_table(folds, begin, end, t.nsteps, nf, t.tab) : -1;
-    *nsteps = t.nsteps;
-    return slot;
-}
 
 bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<int>& fmax,
                      const std::vector<int>& view_sorted, const std::vector<unsigned char>* valid, const std::vector<Run>& runs) {
@@ -1010,7 +853,6 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
     static thread_local std::vector<int> fold_leaf;                       // per sweep fold: the leaf node it takes, -1: none
     fold_leaf.clear();
     if (!c->plan_memo) c->memo.e.clear();                                 // (tables shared within this plan only)
-    std::fill(c->memo.at, c->memo.at + SweepMemo::CAP, -1);
     c->nodes.clear(); c->levels.clear(); c->snodes.clear(); c->sfolds.clear();
     c->sweep_levels.clear(); c->n_group_merges = 0;
     // group exchange: the record [N flags | accepted count | gate bytes (msckf_set_exchange_mask) | N slots of XCHG_SLOT doubles]
@@ -1142,19 +984,20 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
     c->n_group_merges = (int)c->snodes.size();
     // the last merge level goes into the root's launch where that launch exists (k_root_gain: 60-column sweeps, eight fold
     // slots) and its triangles are streamed to the root
-    c->root_streamed = false; c->stream_level = -1; c->h_mflush.clear();
+    bool streamed = false;
+    c->stream_level = -1;
     {
         const int last = n_mlv - 1;
         // (every workgroup of that launch -- root, strips, merge nodes -- holds a CU of its own while it waits for the others:
         //  at most half of the device, so that a partitioned GPU or a kernel on another stream cannot keep a producer out)
         if (c->stream_enabled && mode == 0 && !xchg && last >= 0 && c->sweep_level_nf[last] <= SWEEP_NW_MID && (int)merge_levels[last].size() <= 64 &&
             group_tri.size() > 1 && 2 * (2 + (dc + 15) / 16 + (int)merge_levels[last].size()) <= c->n_cu) {
-            c->root_streamed = true; c->stream_level = last;
+            streamed = true; c->stream_level = last;
         }
         // ... and the leaves with it: ONE merge level (its nodes take leaves only), each node's triangles on the eight fold slots of
         // one round with none adopted (a streamed first triangle is folded), every workgroup of the launch on a CU of its own with
         // the margin root_gain_ok keeps for the root and the strips
-        if (leaf_cand && c->root_streamed && last == 0 && c->n_leaves <= LEAF_FUSED_MAX) {
+        if (leaf_cand && streamed && last == 0 && c->n_leaves <= LEAF_FUSED_MAX) {
             const auto& lv = c->sweep_levels[0];
             int singles = 0;
             for (const Tri& g : group_tri) singles += g.leaf >= 0;
@@ -1178,78 +1021,36 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
             }
         }
     }
-    int root_tab = -1;                                                    // the root's entry of the memo
+    // the root, and in k_sweep form its tables with those of the level that rides in its launch (sweep_root)
     if (!group_tri.empty()) {
-        SweepNode r{};
-        r.fold_begin = (int)c->sfolds.size();
-        int env = 0;
-        for (const Tri& g : group_tri) {
-            env = std::max(env, 6 * g.lo + g.w);
-            SweepFold sf{}; sf.src_off = g.src; sf.off = 6 * g.lo; sf.w = g.w; sf.ew = env - 6 * g.lo; sf.ld = g.ld;
-            if (c->root_streamed && g.lvl == c->stream_level) sf.prod = g.idx + 1;
-            c->sfolds.push_back(sf);
+        static thread_local std::vector<SweepTri> root_tri;
+        root_tri.clear();
+        for (const Tri& g : group_tri) root_tri.push_back({g.src, g.lo, g.w, g.ld, g.lvl == c->stream_level ? g.idx + 1 : 0});
+        SweepRide ride{};
+        if (streamed) {
+            const auto& lv = c->sweep_levels[c->stream_level];
+            ride = SweepRide{&c->snodes[lv.first], lv.second, c->leaf_fused ? SWEEP_NW : c->sweep_level_nf[c->stream_level], c->leaf_fused};
         }
-        r.fold_end = (int)c->sfolds.size();
-        r.wtot = dc;
-        // (k_sweep form: the schedule comes with the flush table and, streamed, the gate table -- all three from the memo)
-        if (mode == 0) root_tab = sweep_tables(c, c->sfolds, r.fold_begin, r.fold_end, dc, SWEEP_NW, !c->root_streamed, c->root_streamed, &r.nsteps);
-        else sweep_schedule(c->sfolds, r.fold_begin, r.fold_end, &r.nsteps, SWEEP_NW, !c->root_streamed);
+        SweepNode r = sweep_root(c->memo, c->sfolds, root_tri, dc, mode == 0, streamed, streamed ? &ride : nullptr, c->plan_tabs);
         c->root_off = head ? 0 : off;
         r.out_off = (long long)c->root_off;
         if (!head) off += (size_t)dc * (dc + 1);
         c->snodes.push_back(r);
         c->root = 0;
     } else {
+        c->plan_tabs.clear();
         c->root = -1;
         c->root_off = 0;
     }
+    c->root_band = c->plan_tabs.band;
     if (head) c->zero_off = head_zero;
     else { c->zero_off = off; off += 16; }
     c->rbuf_doubles = off;
     c->ws_head = head;
     c->xchg_planned = xchg;
     c->h_flush.clear(); c->h_flush_off.clear();
-    c->h_root_flush.clear();
-    c->root_band = 0;
-    if (!group_tri.empty()) {
-        // the root's rows become final one by one as the sweep passes them: K6-K7 (k_gstream.h) follows them block by block
-        const SweepNode& rn = c->snodes.back();
-        for (int g = rn.fold_begin; g < rn.fold_end; ++g) c->root_band = std::max(c->root_band, c->sfolds[g].ew);
-        c->root_n_gate = -1;
-        if (mode == 0) {
-            const SweepTables& rt = c->memo.e[root_tab];
-            c->h_root_flush.assign(rt.tab.begin(), rt.tab.end());
-            c->root_n_gate = rt.n_gate;
-        }
-        if (c->root_streamed) {
-            const auto& lv = c->sweep_levels[c->stream_level];
-            c->h_mflush.assign(lv.second, 0);
-            // (nodes with the same folds -- the same number of triangles of the same widths: most of them -- share one table)
-            // (with the leaves in the launch each table carries the node's gate table and step-0 requirements behind it)
-            const int nf_lv = c->leaf_fused ? SWEEP_NW : c->sweep_level_nf[c->stream_level];
-            for (int i = 0; i < lv.second; ++i) {
-                SweepNode& m = c->snodes[lv.first + i];
-                const int slot = sweep_tables(c, c->sfolds, m.fold_begin, m.fold_end, m.wtot, nf_lv, !c->leaf_fused, c->leaf_fused, &m.nsteps);
-                if (c->memo.at[slot] < 0) {
-                    c->memo.at[slot] = (int)c->h_mflush.size() - lv.second;
-                    c->h_mflush.insert(c->h_mflush.end(), c->memo.e[slot].tab.begin(), c->memo.e[slot].tab.end());
-                }
-                c->h_mflush[i] = c->memo.at[slot];
-                m.n_gate = c->memo.e[slot].n_gate;
-            }
-            c->mflush_at = (int)c->h_root_flush.size();         // (one upload: the merge nodes' tables ride behind the root's)
-            c->h_root_flush.insert(c->h_root_flush.end(), c->h_mflush.begin(), c->h_mflush.end());
-        }
-    }
-    if (mode > 0) {
-        const int rc = 1 << (mode == 1 ? WS_RC_LOG2_4 : WS_RC_LOG2_6);
-        for (const SweepNode& nd : c->snodes) {
-            const size_t o = c->h_flush.size();
-            c->h_flush_off.push_back((int)o);
-            if (!sweep_flush_table(c->sfolds, nd.fold_begin, nd.fold_end, nd.nsteps, nd.wtot, rc, c->h_flush)) return false;
-            sweep_publish_table(c->h_flush, o, nd.nsteps, nd.wtot);
-        }
-    }
+    if (mode > 0 && !sweep_ring_tables(c->sfolds, c->snodes.data(), c->snodes.size(), 1 << (mode == 1 ? WS_RC_LOG2_4 : WS_RC_LOG2_6), c->h_flush, c->h_flush_off))
+        return false;
     return true;
 }
 
@@ -1273,7 +1074,7 @@ void plan_batch(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
     auto tree_only = [&](const std::vector<Run>& runs) {
         c->band_plan = false; c->ws_head = false;
         c->snodes.clear(); c->sfolds.clear(); c->sweep_levels.clear(); c->n_group_merges = 0;
-        c->h_root_flush.clear();
+        c->plan_tabs.clear();
         size_t off_end = 0;
         build_tree(c, fmin, fmax, view_sorted, valid, runs, 0, c->nodes, c->levels, c->root, c->root_off, off_end, c->n_leaves);
         c->rbuf_doubles = off_end;
@@ -1436,6 +1237,16 @@ void launch_wsweep(msckf_ctx* c, int node_base, int count, int rc_log2, int nste
                        c->stream, a);
 }
 
+// what every k_sweep launch names: the tables, the workspace and the zero words at `zero_off` of it
+SweepArgs sweep_args(msckf_ctx* c, size_t zero_off) {
+    SweepArgs a{};
+    a.nodes = ptr<SweepNode>(c->dSweepNodes);
+    a.folds = ptr<SweepFold>(c->dSweepFolds);
+    a.rbuf = ptr<double>(c->dRbuf);
+    a.zero = a.rbuf + zero_off;
+    return a;
+}
+
 int launch_sweeps(msckf_ctx* c, bool with_root = true, int skip_level = -1) {
     if (c->snodes.empty()) return MSCKF_OK;
     if (c->sweep_mode > 0) {
@@ -1448,12 +1259,8 @@ int launch_sweeps(msckf_ctx* c, bool with_root = true, int skip_level = -1) {
         HIPCHK(c, hipGetLastError());
         return MSCKF_OK;
     }
-    SweepArgs a{};
-    a.nodes = ptr<SweepNode>(c->dSweepNodes);
-    a.folds = ptr<SweepFold>(c->dSweepFolds);
-    a.rbuf = ptr<double>(c->dRbuf);
+    SweepArgs a = sweep_args(c, c->zero_off);              // (zero: inside the plan's zero-initialised, never written region)
     a.stamps = c->dStamps.p ? ptr<long long>(c->dStamps) : nullptr;
-    a.zero = ptr<double>(c->dRbuf) + c->zero_off;          // inside the plan's (zero-initialised, never written) region
     const dim3 block(64 * SWEEP_NW * SWEEP_WPF);
     for (size_t li = 0; li < c->sweep_levels.size(); ++li) {
         if ((int)li == skip_level) continue;               // (inside k_root_gain's launch, streamed to the root)
@@ -1487,7 +1294,7 @@ int upload_plan(msckf_ctx* c) {
     size_t need = 0;
     auto room = [&](size_t bytes) { const size_t o = need; need += (std::max<size_t>(bytes, 64) + 255) & ~(size_t)255; return o; };
     const size_t b_nodes = c->nodes.size() * sizeof(FoldNode), b_sn = c->snodes.size() * sizeof(SweepNode), b_sf = c->sfolds.size() * sizeof(SweepFold);
-    const size_t b_rf = c->h_root_flush.size() * 4, b_fl = c->h_flush.size() * 4, b_fo = c->h_flush_off.size() * 4;
+    const size_t b_rf = c->plan_tabs.image.size() * 4, b_fl = c->h_flush.size() * 4, b_fo = c->h_flush_off.size() * 4;
     const size_t b_rn = c->rnodes.size() * sizeof(FoldNode);
     const size_t o_nodes = room(b_nodes), o_sn = room(b_sn), o_sf = room(b_sf), o_rf = room(b_rf), o_fl = room(b_fl), o_fo = room(b_fo);
     const size_t o_rn = room(b_rn);
@@ -1510,7 +1317,7 @@ int upload_plan(msckf_ctx* c) {
     if (b_nodes) std::memcpy(hp + o_nodes, c->nodes.data(), b_nodes);
     if (b_sn) std::memcpy(hp + o_sn, c->snodes.data(), b_sn);
     if (b_sf) std::memcpy(hp + o_sf, c->sfolds.data(), b_sf);
-    if (b_rf) std::memcpy(hp + o_rf, c->h_root_flush.data(), b_rf);
+    if (b_rf) std::memcpy(hp + o_rf, c->plan_tabs.image.data(), b_rf);
     if (b_fl) std::memcpy(hp + o_fl, c->h_flush.data(), b_fl);
     if (b_fo) std::memcpy(hp + o_fo, c->h_flush_off.data(), b_fo);
     if (b_rn) std::memcpy(hp + o_rn, c->rnodes.data(), b_rn);
@@ -1946,6 +1753,12 @@ bool root_gain_ok(const msckf_ctx* c, int band) {
 // ([count offsets | tables]) and the root's step-0 requirement count behind its own tables (sweep_gate_table).
 // leaves: the leaves ride too (k_leaf_root_gain), the merge nodes polling them.
 struct MergeRide { int node_base, count, nf, n_gate; const int* flush; size_t lds; };    // lds: what its largest node asks for
+// ... of the `count` nodes at `nodes` (the launch's nodes from node_base on), their tables in the image `dev` of `t`
+MergeRide merge_ride(const SweepNode* nodes, int node_base, int count, int nf, const RootTables& t, const int* dev, bool gated) {
+    MergeRide r{node_base, count, nf, t.n_gate, dev + t.merge_at, 0};
+    for (int i = 0; i < count; ++i) r.lds = std::max(r.lds, sweep_lds_bytes_fl(nodes[i].wtot, nf, nodes[i].nsteps, gated ? nodes[i].n_gate : -1));
+    return r;
+}
 int launch_root_and_gain(msckf_ctx* c, SweepArgs sa, int wtot, int nsteps, const int* flush_tab, const GainSources& gsrc,
                          const MergeRide* ride = nullptr, bool leaves = false) {
     ++c->gs_epoch;
@@ -2110,7 +1923,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     if (c->F > 0 && c->wide_on_stream2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_wfeat, 0));
     // the leaves inside the root's launch (k_leaf_root_gain): a plan made for it (no split long tracks) whose root runs beside K6-K7
     const bool fuse_leaves = c->F > 0 && c->band_plan && c->leaf_fused && with_gain && c->root >= 0 && c->sweep_mode == 0 &&
-                             gstream_ok(c, c->root_band) && !c->h_root_flush.empty() && root_gain_ok(c, c->root_band);
+                             gstream_ok(c, c->root_band) && !c->plan_tabs.image.empty() && root_gain_ok(c, c->root_band);
     rec.fused_leaves = fuse_leaves;
     if (c->F > 0 && c->band_plan && !fuse_leaves && (rc = launch_leaves_band(c, early ? c->n_leaves0 : 0)) != MSCKF_OK) return rc;
     if (c->F > 0 && !c->band_plan && (rc = launch_fold_levels(c, c->levels, c->nodes)) != MSCKF_OK) return rc;
@@ -2143,8 +1956,8 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     //  ~ U[2, 30]: 695 -> ~610 us)
     static const bool t2_split = [] { const char* e = std::getenv("MSCKF_T2_SPLIT_ROOT"); return !e || std::atoi(e) != 0; }();
     const bool beside = gs && c->band_plan && c->root >= 0 && !(t2_early && t2_split) &&
-                        (c->sweep_mode == 0 ? (!c->h_root_flush.empty() && root_gain_ok(c, c->root_band)) : root_gain_w_ok(c, c->root_band));
-    const bool streamed = beside && c->sweep_mode == 0 && c->root_streamed;     // the last merge level rides in the root's launch
+                        (c->sweep_mode == 0 ? (!c->plan_tabs.image.empty() && root_gain_ok(c, c->root_band)) : root_gain_w_ok(c, c->root_band));
+    const bool streamed = beside && c->sweep_mode == 0 && c->plan_tabs.streamed;     // the last merge level rides in the root's launch
     if (fuse_leaves && !streamed) { c->last_error = "k_leaf_root_gain: the root does not run beside K6-K7"; return MSCKF_ERR_STATE; }
     if (c->F > 0 && c->band_plan && (rc = launch_sweeps(c, (with_gain || !c->xchg_planned) && !beside, streamed ? c->stream_level : -1)) != MSCKF_OK) return rc;
     if (c->F > 0 && c->xchg_planned && !with_gain) {       // the accepted count rides in the export record (double N)
@@ -2165,20 +1978,14 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
         if (rc != MSCKF_OK) return rc;
         if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[2], c->stream));
     } else if (beside) {
-        SweepArgs a{};
-        a.nodes = ptr<SweepNode>(c->dSweepNodes);
-        a.folds = ptr<SweepFold>(c->dSweepFolds);
-        a.rbuf = ptr<double>(c->dRbuf);
-        a.zero = ptr<double>(c->dRbuf) + c->zero_off;
+        SweepArgs a = sweep_args(c, c->zero_off);
         a.node_base = c->n_group_merges;
         // (one launch: the stage boundary K5 | K6-K7 is not observable; the events report the pair under K5 and only what
         //  trails the launch -- nothing -- under K6-K7)
         MergeRide ride{};
         if (streamed) {
             const auto& lv = c->sweep_levels[c->stream_level];
-            ride = MergeRide{lv.first, lv.second, c->sweep_level_nf[c->stream_level], c->root_n_gate, ptr<int>(c->dRootFlush) + c->mflush_at, 0};
-            for (int i = lv.first; i < lv.first + lv.second; ++i)
-                ride.lds = std::max(ride.lds, sweep_lds_bytes_fl(c->snodes[i].wtot, ride.nf, c->snodes[i].nsteps, fuse_leaves ? c->snodes[i].n_gate : -1));
+            ride = merge_ride(&c->snodes[lv.first], lv.first, lv.second, c->sweep_level_nf[c->stream_level], c->plan_tabs, ptr<int>(c->dRootFlush), fuse_leaves);
         }
         if ((rc = launch_root_and_gain(c, a, c->snodes.back().wtot, c->snodes.back().nsteps, ptr<int>(c->dRootFlush), src,
                                        streamed ? &ride : nullptr, fuse_leaves)) != MSCKF_OK) return rc;
@@ -3177,7 +2984,7 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
         st->stacked_rows = counters[1]; st->not_spd = counters[2];
         st->n_leaves = c->n_leaves;
         st->n_levels = (int)c->levels.size() + (c->band_plan ? (int)c->sweep_levels.size() + 1 : 0);
-        st->k5_launches = st->n_levels - ((c->band_plan && r.fused_root && c->sweep_mode == 0 && c->root_streamed) ? 1 : 0)   // (a streamed merge level rides in the root's launch)
+        st->k5_launches = st->n_levels - ((c->band_plan && r.fused_root && c->sweep_mode == 0 && c->plan_tabs.streamed) ? 1 : 0)   // (a streamed merge level rides in the root's launch)
                           - ((c->band_plan && r.fused_root && r.fused_leaves) ? 1 : 0);                                  // (... and the leaves with it)
         st->us_total = c->us_total; st->us_feature = c->us_stage[0]; st->us_qr = c->us_stage[1];
         st->us_gain = c->us_stage[2];
@@ -4415,9 +4222,7 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
                        c->x_key == key;
     if (!reuse) {
         c->x_snodes.clear(); c->x_sfolds.clear();
-        const int fold_base = (int)c->sfolds.size();      // the tables sit behind the local plan's
-        struct Tri { long long src; int lo, w; int prod = 0, ld = 0; };
-        std::vector<Tri> groups;
+        std::vector<SweepTri> groups;
         std::vector<SweepFold>& fl = c->x_sfolds;
         for (int s0 = 0; s0 < N; ++s0) {
             const int w = 6 * (std::min(s0 + XW / 6, N) - s0);
@@ -4425,72 +4230,42 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
             for (int r = 0; r < n_rec; ++r)
                 if (key[(size_t)r * N + s0] != 0.0) src.push_back(rec_base + (long long)((size_t)r * rec + rec_head(c) + (size_t)s0 * XCHG_SLOT));
             if (src.empty()) continue;
-            if (src.size() == 1) { groups.push_back({src[0], s0, w}); continue; }
+            if (src.size() == 1) { groups.push_back({src[0], s0, w, 0, 0}); continue; }
             SweepNode m{};
-            m.fold_begin = fold_base + (int)fl.size();
-            const int b = (int)fl.size();
+            m.fold_begin = (int)fl.size();
             for (long long so : src) { SweepFold sf{}; sf.src_off = so; sf.off = 0; sf.w = w; sf.ew = w; fl.push_back(sf); }
-            m.fold_end = fold_base + (int)fl.size();
+            m.fold_end = (int)fl.size();
             m.wtot = w;
-            sweep_schedule(fl, b, (int)fl.size(), &m.nsteps);
+            sweep_schedule(fl, m.fold_begin, m.fold_end, &m.nsteps);
             m.out_off = (long long)(o_mrg + (size_t)s0 * MSLOT);
             m.ldo = xs ? 64 : 0;
             c->x_snodes.push_back(m);
-            groups.push_back({m.out_off, s0, w, (int)c->x_snodes.size(), m.ldo});
+            groups.push_back({m.out_off, s0, w, m.ldo, (int)c->x_snodes.size()});
         }
         c->x_n_merges = (int)c->x_snodes.size();
         // the merge level rides in the root's launch and streams its rows to the root (as the local plan's last level does)
-        c->x_streamed = xs && c->x_n_merges >= 1 && c->x_n_merges <= 64 && groups.size() > 1 && root_gain_ok(c, XW) &&
-                        2 * (2 + (dc + 15) / 16 + c->x_n_merges) <= c->n_cu && !early;     // (an early update: the root sweep alone)
+        const bool streamed = xs && c->x_n_merges >= 1 && c->x_n_merges <= 64 && groups.size() > 1 && root_gain_ok(c, XW) &&
+                              2 * (2 + (dc + 15) / 16 + c->x_n_merges) <= c->n_cu && !early;     // (an early update: the root sweep alone)
+        c->merge_tabs.clear();
         if (!groups.empty()) {
-            SweepNode r{};
-            r.fold_begin = fold_base + (int)fl.size();
-            const int b = (int)fl.size();
-            int env = 0;
-            for (const Tri& g : groups) {
-                env = std::max(env, 6 * g.lo + g.w);
-                SweepFold sf{}; sf.src_off = g.src; sf.off = 6 * g.lo; sf.w = g.w; sf.ew = env - 6 * g.lo; sf.ld = g.ld;
-                if (c->x_streamed) sf.prod = g.prod;
-                fl.push_back(sf);
-            }
-            r.fold_end = fold_base + (int)fl.size();
-            r.wtot = dc;
-            sweep_schedule(fl, b, (int)fl.size(), &r.nsteps, SWEEP_NW, !c->x_streamed);
+            if (!c->plan_memo) c->memo.e.clear();
+            SweepRide ride{c->x_snodes.data(), c->x_n_merges, SWEEP_NW, false};
+            SweepNode r = sweep_root(c->memo, fl, groups, dc, xmode == 0, streamed, &ride, c->merge_tabs);
             r.out_off = (long long)o_root;
             c->x_snodes.push_back(r);
-            c->x_root_flush.clear();
-            if (xmode == 0) sweep_flush_table(fl, b, (int)fl.size(), r.nsteps, r.wtot, 1 << 29, c->x_root_flush);
-            c->x_root_n_gate = -1;
-            if (c->x_streamed) {
-                c->x_root_n_gate = sweep_gate_table(fl, b, (int)fl.size(), r.nsteps, SWEEP_NW, c->x_root_flush);
-                c->x_mflush_at = (int)c->x_root_flush.size();
-                const int nm = c->x_n_merges;
-                c->x_root_flush.resize(c->x_root_flush.size() + nm, 0);
-                for (int i = 0; i < nm; ++i) {
-                    const SweepNode& m = c->x_snodes[i];
-                    c->x_root_flush[c->x_mflush_at + i] = (int)c->x_root_flush.size() - c->x_mflush_at - nm;
-                    sweep_flush_table(fl, m.fold_begin - fold_base, m.fold_end - fold_base, m.nsteps, m.wtot, 1 << 29, c->x_root_flush);
-                }
-            }
         }
-        // tables: local plan first (its launches may follow this call), the merge plan behind it
+        // tables: local plan first (its launches may follow this call), the merge plan behind it, its folds counted on from theirs
         std::vector<SweepNode> all_n(c->snodes);
-        all_n.insert(all_n.end(), c->x_snodes.begin(), c->x_snodes.end());
+        for (SweepNode nd : c->x_snodes) { nd.fold_begin += (int)c->sfolds.size(); nd.fold_end += (int)c->sfolds.size(); all_n.push_back(nd); }
         std::vector<SweepFold> all_f(c->sfolds);
         all_f.insert(all_f.end(), fl.begin(), fl.end());
         if (xmode > 0) {
             // k_wsweep: which rows of R leave the ring at the head of every macro step (tables behind the local plan's)
-            const int rc = 1 << (xmode == 1 ? WS_RC_LOG2_4 : WS_RC_LOG2_6);
             std::vector<int> fl_tab(c->h_flush), fl_off(c->h_flush_off);
             fl_off.resize(c->snodes.size(), 0);
-            for (const SweepNode& nd : c->x_snodes) {
-                const size_t o = fl_tab.size();
-                fl_off.push_back((int)o);
-                if (!sweep_flush_table(fl, nd.fold_begin - fold_base, nd.fold_end - fold_base, nd.nsteps, nd.wtot, rc, fl_tab)) {
-                    c->last_error = "merge plan: the band does not fit the ring of k_wsweep";
-                    return MSCKF_ERR_ARG;
-                }
-                sweep_publish_table(fl_tab, o, nd.nsteps, nd.wtot);
+            if (!sweep_ring_tables(fl, c->x_snodes.data(), c->x_snodes.size(), 1 << (xmode == 1 ? WS_RC_LOG2_4 : WS_RC_LOG2_6), fl_tab, fl_off)) {
+                c->last_error = "merge plan: the band does not fit the ring of k_wsweep";
+                return MSCKF_ERR_ARG;
             }
             if (int rc2 = ensure(c, c->dFlush, fl_tab.size() * 4)) return rc2;
             if (int rc2 = ensure(c, c->dFlushOff, fl_off.size() * 4)) return rc2;
@@ -4502,9 +4277,9 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         if (int rc = ensure(c, c->dSweepFolds, std::max<size_t>(all_f.size(), 1) * sizeof(SweepFold))) return rc;
         if (!all_n.empty()) HIPCHK(c, hipMemcpyAsync(c->dSweepNodes.p, all_n.data(), all_n.size() * sizeof(SweepNode), hipMemcpyHostToDevice, c->stream));
         if (!all_f.empty()) HIPCHK(c, hipMemcpyAsync(c->dSweepFolds.p, all_f.data(), all_f.size() * sizeof(SweepFold), hipMemcpyHostToDevice, c->stream));
-        if (!c->x_root_flush.empty()) {
-            if (int rc = ensure(c, c->dXRootFlush, c->x_root_flush.size() * 4)) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->dXRootFlush.p, c->x_root_flush.data(), c->x_root_flush.size() * 4, hipMemcpyHostToDevice, c->stream));
+        if (!c->merge_tabs.image.empty()) {
+            if (int rc = ensure(c, c->dXRootFlush, c->merge_tabs.image.size() * 4)) return rc;
+            HIPCHK(c, hipMemcpyAsync(c->dXRootFlush.p, c->merge_tabs.image.data(), c->merge_tabs.image.size() * 4, hipMemcpyHostToDevice, c->stream));
         }
         HIPCHK(c, hipMemsetAsync(rb + o_mrg, 0, (o_end - o_mrg) * 8, c->stream));   // merged triangles, root block, zero words
         HIPCHK(c, hipStreamSynchronize(c->stream));                                  // all_n / all_f are locals
@@ -4576,15 +4351,10 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         if (rcg != MSCKF_OK) return rcg;
     } else {
         gsrc.first = rb + c->x_root_off;
-        SweepArgs a{};
-        a.nodes = ptr<SweepNode>(c->dSweepNodes);
-        a.folds = ptr<SweepFold>(c->dSweepFolds);
-        a.rbuf = rb;
-        a.stamps = nullptr;
-        a.zero = rb + c->x_zero_off;
+        SweepArgs a = sweep_args(c, c->x_zero_off);
         const dim3 block(64 * SWEEP_NW * SWEEP_WPF);
-        const bool fused = root_gain_ok(c, XW) && !c->x_root_flush.empty() && !early;
-        const bool ride_on = fused && c->x_streamed;
+        const bool fused = root_gain_ok(c, XW) && !c->merge_tabs.image.empty() && !early;
+        const bool ride_on = fused && c->merge_tabs.streamed;
         if (c->x_n_merges > 0 && !ride_on) {
             a.node_base = nb;
             hipLaunchKernelGGL((k_sweep<SWEEP_NW, SWEEP_WPF>), dim3(c->x_n_merges), block,
@@ -4594,11 +4364,7 @@ int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int devic
         int rc;
         if (fused) {
             MergeRide ride{};
-            if (ride_on) {
-                ride = MergeRide{nb, c->x_n_merges, SWEEP_NW, c->x_root_n_gate, ptr<int>(c->dXRootFlush) + c->x_mflush_at, 0};
-                for (int i = 0; i < c->x_n_merges; ++i)
-                    ride.lds = std::max(ride.lds, sweep_lds_bytes_fl(c->x_snodes[i].wtot, SWEEP_NW, c->x_snodes[i].nsteps));
-            }
+            if (ride_on) ride = merge_ride(c->x_snodes.data(), nb, c->x_n_merges, SWEEP_NW, c->merge_tabs, ptr<int>(c->dXRootFlush), false);
             rc = launch_root_and_gain(c, a, dc, c->x_snodes.back().nsteps, ptr<int>(c->dXRootFlush), gsrc, ride_on ? &ride : nullptr);
         } else {
             hipLaunchKernelGGL((k_sweep<SWEEP_NW, SWEEP_WPF, SWEEP_P2P>), dim3(1), block, sweep_lds_bytes(dc, SWEEP_NW, SWEEP_WPF), c->stream, a);

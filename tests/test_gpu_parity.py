@@ -645,6 +645,33 @@ def test_shipped_merge_path_logical_shards(N, F, M, S, kw):
         assert one.status in (0, 1)
 
 
+def test_merge_nodes_that_share_a_table_and_one_that_does_not(monkeypatch):
+    """Rank 0's merge plan takes its root and its merge nodes' tables from the planner's memo (`sweep_root`): cross-rank
+    merge nodes with the same folds share one table of the uploaded image.  N = 12, 120 tracks of 2 to 6 views over three
+    shards cut so that the groups of slots 0, 1, 2 (windows of ten slots: equal triangles) get a triangle from every shard and
+    others from two: equal to the oracle, and bit for bit the merge of an engine that keeps no memo."""
+    from msckf_amd import synth
+    from msckf_amd.api import UpdateEngine
+    from msckf_amd.shard import shard_group_flags
+    from oracle import msckf_oracle as oracle
+    N = 12
+    prob = synth.make_problem(N, 120, 6, seed=71, variable_tracks=True)
+    ref = oracle.update(prob, dense_noise=False)
+    shards = [(0, 30), (30, 50), (50, 120)]
+    per_group = shard_group_flags(prob, shards).sum(axis=0)
+    assert (per_group[:N - 10 + 1] == 3).sum() >= 2 and (per_group == 2).sum() >= 1 and (per_group[:N - 10 + 1] == 2).sum() == 0
+    results = []
+    for memo in (True, False):
+        if not memo:
+            monkeypatch.setenv("MSCKF_PLAN_MEMO", "0")
+        with UpdateEngine(max_clones=N, max_features=128, max_track=6) as e:
+            assert e.band_ok(prob)
+            results.append(_shipped_merge(e, prob, shards, ref))
+    a, b = results
+    assert a.status == b.status == 0
+    assert np.array_equal(a.dx, b.dx) and np.array_equal(a.P_new, b.P_new) and np.array_equal(a.accepted, b.accepted)
+
+
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_shipped_merge_path_config5_full_size(dtype):
     """BASELINE.json configs[4] (N = 50, 20000 features, track 15) split over 8 logical shards, in fp64 and as specified

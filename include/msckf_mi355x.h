@@ -55,9 +55,13 @@ extern "C" {
 #define MSCKF_ERR_ARG (-1)          /* bad argument / size over the context's capacity      */
 #define MSCKF_ERR_HIP (-2)          /* HIP runtime failure (msckf_last_error has the text)  */
 #define MSCKF_ERR_NO_DEVICE (-3)    /* no usable gfx950 device                              */
-#define MSCKF_ERR_NOT_SPD (-4)      /* innovation covariance S not positive definite (the
-                                       reference would raise numpy.linalg.LinAlgError,
-                                       MSCKF.py:562/:606)                                   */
+#define MSCKF_ERR_NOT_SPD (-4)      /* the joint innovation covariance S of the stacked rows is
+                                       not positive definite: K6-K7 met a pivot that is not a
+                                       positive normal number.  dx = 0, P_out = the prior.  (The
+                                       reference inverts such an S as it is, MSCKF.py:606;
+                                       numpy.linalg.inv raises for an exactly singular one only.)
+                                       A single track's gate matrix that is not SPD is no error:
+                                       see msckf_stats.not_spd                               */
 #define MSCKF_ERR_STATE (-5)        /* call order (e.g. run before set_state/set_features)  */
 #define MSCKF_ERR_DUP_SLOT (-6)     /* a track observes the same clone slot twice           */
 
@@ -106,7 +110,13 @@ typedef struct msckf_stats {
     int32_t stacked_rows;           /* m = sum of q_j over accepted features                */
     int32_t n_leaves;
     int32_t n_levels;               /* levels of the K5 plan (tree levels, or leaves + group merge levels + root sweep) */
-    int32_t not_spd;                /* per-feature gate matrices that were not SPD          */
+    int32_t not_spd;                /* tracks whose gate matrix S_j = H_o P H_o^T + sigma^2 I met a pivot that is not > 0
+                                       (an indefinite or non-finite S_j; a NaN or infinite inverse-depth point ends here,
+                                       a NaN or infinite observation in n_rejected: its S_j is sound, its gamma is NaN).
+                                       The contract: such a track is dropped BEFORE the chi-square test, counted here and
+                                       NOT in n_rejected, its accepted[] byte is 0, and dx / P_out are those of the batch
+                                       without it.  A deliberate departure from the reference, which inverts whatever S_j
+                                       it gets and gates on the number that comes out (MSCKF.py:561-568)               */
     int32_t k5_launches;            /* launches they took in the last run (a merge level streamed to the root rides in its launch) */
     float us_total;                 /* whole device pipeline                                */
     float us_feature;               /* K1-K3 kernel                                         */
@@ -534,6 +544,11 @@ int msckf_import_covariance(msckf_ctx* ctx, const void* P, int device_ptr);
 /* ---- introspection for tests (device intermediates, host copies) -------- */
 /* gamma[F] (gate statistic), qdim[F] (dof = projected rows), in input order. */
 int msckf_debug_gate(msckf_ctx* ctx, double* gamma, int32_t* qdim);
+/* The gate's verdict per track as k_feature wrote it, input order: 1 accepted, 0 rejected by the chi-square test, 2 gate
+ * matrix not SPD (msckf_stats.not_spd), 3 not selected by msckf_run_select -- msckf_get_result's accepted[] folds 0 / 2 / 3
+ * into 0.  n_blocks (nullable): the narrow and remainder blocks of the batch's split long tracks; block_codes / block_track
+ * (nullable, n_blocks entries each): the byte every block inherited and the input index of its track. */
+int msckf_debug_gate_codes(msckf_ctx* ctx, uint8_t* codes, int32_t* n_blocks, uint8_t* block_codes, int32_t* block_track);
 /* Final compressed system: T (6N x 6N, upper triangular) and r_n (6N). */
 int msckf_debug_compressed(msckf_ctx* ctx, double* T, double* rn);
 /* Diagnostics: out == NULL enables per-node cycle stamps in the fold kernel; otherwise copies

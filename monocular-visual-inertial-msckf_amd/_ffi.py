@@ -26,7 +26,7 @@ SYMBOLS = [
     "msckf_update", "msckf_set_state", "msckf_set_features", "msckf_run", "msckf_run_timed", "msckf_sync",
     "msckf_get_result", "msckf_commit_covariance", "msckf_run_compress", "msckf_block_doubles",
     "msckf_export_block", "msckf_run_merge_gain", "msckf_set_group_exchange", "msckf_band_rule", "msckf_group_record_doubles",
-    "msckf_export_groups", "msckf_run_merge_groups", "msckf_run_merge_groups_flags", "msckf_export_result", "msckf_import_covariance", "msckf_debug_gate", "msckf_debug_compressed", "msckf_debug_fold_stamps",
+    "msckf_export_groups", "msckf_run_merge_groups", "msckf_run_merge_groups_flags", "msckf_export_result", "msckf_import_covariance", "msckf_debug_gate", "msckf_debug_gate_codes", "msckf_debug_compressed", "msckf_debug_fold_stamps",
     "msckf_device_pointer", "msckf_stream",
     "msckf_set_tracks", "msckf_run_select", "msckf_clear_selection", "msckf_get_selection",
     "msckf_debug_time_select", "msckf_replan", "msckf_run_associate",
@@ -194,6 +194,8 @@ def load():
     lib.msckf_import_covariance.restype = C.c_int
     lib.msckf_debug_gate.argtypes = [vp, _dp, _ip]
     lib.msckf_debug_gate.restype = C.c_int
+    lib.msckf_debug_gate_codes.argtypes = [vp, _up, _ip, _up, _ip]
+    lib.msckf_debug_gate_codes.restype = C.c_int
     lib.msckf_debug_compressed.argtypes = [vp, _dp, _dp]
     lib.msckf_debug_compressed.restype = C.c_int
     lib.msckf_debug_fold_stamps.argtypes = [vp, C.POINTER(C.c_longlong), C.c_int32]

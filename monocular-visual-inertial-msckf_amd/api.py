@@ -769,13 +769,23 @@ class UpdateEngine:
         self._F_total = int(b[-1])
 
     def gate_bytes(self) -> np.ndarray:
-        """Gate byte per feature of the loaded batch, input order: 1 accepted, 0 otherwise (the group records
-        carry the finer codes 2 = gate matrix not SPD, 3 = not selected; this host read-back, used by the
-        root-block fallback exchange only, folds them into 0)."""
-        st = _ffi.Stats()
-        acc = np.zeros(max(self._F, 1), dtype=np.uint8)
-        self._check(self._lib.msckf_get_result(self._h, None, None, _ffi.uptr(acc), C.byref(st)))
-        return acc[:self._F]
+        """Gate byte per feature of the loaded batch, input order, as the group records carry them: 1 accepted, 0 rejected
+        by the chi-square test, 2 gate matrix not SPD, 3 not selected (the root-block fallback exchange ships them, so
+        that `shared_result` counts `n_rejected` and `not_spd` as every other path does)."""
+        return self.gate_codes()[0]
+
+    def gate_codes(self):
+        """(codes (F,) uint8 in input order, block_codes, block_track): the gate's verdict per track and, for the narrow
+        and remainder blocks of split long tracks, the byte each inherited and the input index of its track."""
+        F = self._F
+        nb = C.c_int32(0)
+        codes = np.zeros(max(F, 1), dtype=np.uint8)
+        self._check(self._lib.msckf_debug_gate_codes(self._h, _ffi.uptr(codes), C.addressof(nb), None, None), allow_noop=False)
+        n = int(nb.value)
+        bc, bt = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int32)
+        if n:
+            self._check(self._lib.msckf_debug_gate_codes(self._h, None, None, _ffi.uptr(bc), _ffi.iptr(bt)), allow_noop=False)
+        return codes[:F].copy(), bc[:n].copy(), bt[:n].copy()
 
     def result_range_doubles(self) -> int:
         return int(self._lib.msckf_result_range_doubles(self._h))

@@ -2978,8 +2978,9 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
     if (st) {
         std::memset(st, 0, sizeof(*st));
         st->n_features = c->F - counters[3]; st->n_accepted = n_acc;
-        // features whose gate matrix was not SPD never reached the chi-square test (the reference would have raised
-        // LinAlgError at MSCKF.py:562): they are reported in not_spd, not counted as gate rejections (:578)
+        // features whose gate matrix met a pivot that is not > 0 never reached the chi-square test: they are reported in not_spd,
+        // not counted as gate rejections (:578).  A deliberate departure: the reference inverts whatever S it gets and gates on
+        // the number that comes out (MSCKF.py:561-568; np.linalg.inv raises for an exactly singular S only)
         st->n_rejected = std::max(0, c->F - counters[3] - n_acc - counters[2]);
         st->stacked_rows = counters[1]; st->not_spd = counters[2];
         st->n_leaves = c->n_leaves;
@@ -4582,6 +4583,24 @@ int msckf_debug_gate(msckf_ctx* c, double* gamma, int32_t* qdim) {
         const int f = c->perm[s];
         if (gamma) gamma[f] = g[s];
         if (qdim) qdim[f] = 2 * (c->h_view_sorted[s + 1] - c->h_view_sorted[s]) - rk[s];
+    }
+    return MSCKF_OK;
+}
+
+int msckf_debug_gate_codes(msckf_ctx* c, uint8_t* codes, int32_t* n_blocks, uint8_t* block_codes, int32_t* block_track) {
+    if (!c || !c->last.ran) return MSCKF_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->wide_on_stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+    const int F = c->F, Fs = c->F > 0 ? c->Fs : 0;
+    if (n_blocks) *n_blocks = Fs - F;
+    if (F == 0) return MSCKF_OK;
+    std::vector<unsigned char> a(Fs);
+    HIPCHK(c, hipMemcpy(a.data(), c->dAcc.p, (size_t)Fs, hipMemcpyDeviceToHost));
+    if (codes) for (int s = 0; s < F; ++s) codes[c->perm[s]] = a[s];
+    for (int e = F; e < Fs; ++e) {
+        if (block_codes) block_codes[e - F] = a[e];
+        if (block_track) block_track[e - F] = c->perm[c->h_parent[e - F]];
     }
     return MSCKF_OK;
 }

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include "wave_ops.h"
 #include "feature_dpp_groups.h"
+#include "batch_order.h"          // SplitRec, SPLIT_MAXG, SPLIT_GSLOTS
 
 namespace msckf {
 
@@ -35,15 +36,8 @@ namespace msckf {
 //            -- the "remainder block", a few rows per long track instead of 2 M - 3.
 // A 30-view track becomes 3 x 17 narrow rows + 6 remainder rows; the gate (K3) is taken over all of them together and does
 // not depend on the basis either, so it runs on the one-level basis as before.
-constexpr int SPLIT_MAXG = 6;            // groups per long track
-constexpr int SPLIT_GSLOTS = 10;         // clone slots a group may span
-struct __attribute__((aligned(8))) SplitRec {
-    int child[SPLIT_MAXG];               // block index (K5 order) of group g's narrow block; -1: a one-view group has none
-    int wide;                            // block index of the remainder block
-    unsigned char gv[SPLIT_MAXG + 1];    // group g = views [gv[g], gv[g + 1]) of the track (views in slot order)
-    unsigned char ng;                    // groups (>= 2)
-    int rows_cap;                        // 3 ng: the rows the remainder block may hold (its place in the dense matrix is found by k_rem_scatter)
-};
+// (SPLIT_MAXG groups per long track, SPLIT_GSLOTS clone slots a group may span, one SplitRec per long track: batch_order.h,
+//  where the host cuts the groups)
 
 struct FeatureArgs {
     int F;                       // features in this launch

@@ -11,16 +11,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "k_lsweep.h"
+#include "batch_order.h"          // GatherRec
 
 namespace msckf {
-
-struct __attribute__((aligned(8))) GatherRec {
-    int f;                        // input index of the track at this sorted position
-    int a;                        // its first view in the caller's arrays
-    int M;                        // views
-    int o;                        // its first view in the sorted arrays
-    long long blk;                // offset of its K4 block
-};
 
 struct GatherArgs {
     // the caller's arrays, input order (uv: HBM, uploaded by DMA; the others: the pinned host image)

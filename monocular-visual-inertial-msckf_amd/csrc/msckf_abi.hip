@@ -41,6 +41,7 @@
 #include "k_match.h"
 #include "run_outcome.h"
 #include "track_mirror.h"
+#include "batch_order.h"
 
 static_assert(TrackMirror::kOk == MSCKF_OK && TrackMirror::kErrArg == MSCKF_ERR_ARG && TrackMirror::kErrDupSlot == MSCKF_ERR_DUP_SLOT,
               "track_mirror.h returns the ABI's codes");
@@ -297,7 +298,7 @@ struct msckf_ctx {
     int maxN = 0, maxF = 0, maxM = 0;
     int maxV = 0;                         // views a row of the track store holds: max_track, which may be MSCKF_MAX_TRACK + 1 (a batch track: maxM)
     // current problem
-    int N = 0, d = 0, dc = 0, F = 0, sumM = 0, Mmax = 0;
+    int N = 0, d = 0, dc = 0, F = 0, sumM = 0;
     bool have_state = false, have_features = false;
     RunRecord last;                       // the last run (finish_run)
     ncclComm_t comm = nullptr;            // RCCL communicator of the sharded update (msckf_comm_init)
@@ -314,7 +315,7 @@ struct msckf_ctx {
     Buf dLineBase, dLineDir, dLineConf, dLostFor, dTrackedFor, dSelFlags, dWorld;   // f1 (k_select)
     Buf dY, dS, dL, dU, dInvd, dK, dB2, dD, dPn, dDx, dCholWork, dStatus;
     // host-side plan
-    std::vector<int> perm;                // sorted position -> input index
+    BatchOrder ord;                       // the current batch in the pipeline's order (batch_order.h); valid under have_features
     std::vector<FoldNode> nodes;
     std::vector<std::pair<int, int>> levels;   // (node_base, count) per fold launch
     int root = -1;
@@ -337,7 +338,6 @@ struct msckf_ctx {
     int plan_N = -1;
     bool plan_xchg = false;
     std::vector<int> plan_fmin, plan_fmax, plan_view;
-    long long stack_elems = 0;            // scalars of the current batch's stack blocks (a zero word follows them)
     int leaf_nf = 8;                      // row blocks in flight per 60-column leaf workgroup (8 or 12)
     bool leaf_tall = false;               // 90-column leaves with 56-row blocks (k_lsweep<8, 6, LS_RS6T>)
     bool leaf_narrow = false, leaf_wide = false;      // band plan: leaf nodes with w + 1 <= 64 / > 64 exist
@@ -378,9 +378,7 @@ struct msckf_ctx {
     float us_host_prep = 0, us_h2d = 0, us_d2h = 0;
     float us_stage[3] = {0, 0, 0};
     float us_total = 0;
-    std::vector<int> h_view_sorted;
     std::vector<int> h_view_in;           // view_ptr as the caller gave it (set_tracks permutes with it)
-    std::vector<int> h_fmin, h_fmax;      // first / last slot per sorted feature (msckf_replan)
     bool have_tracks = false, use_select = false;
     msckf_select_params sel_params{};     // of the last msckf_run_select
     std::vector<double> h_cam[4];         // host mirror of cam_R / cam_t / cam_R0 / cam_t0 (clone bookkeeping, f2)
@@ -412,20 +410,9 @@ struct msckf_ctx {
     bool gs_overlap = true;               // MSCKF_GAIN_OVERLAP=0: k_gain_stream as a launch of its own behind the root sweep
     int root_band = 0;                    // widest row of the root block in columns (band plan: plan_tabs.band; tree plan: dc)
     bool gs_stamp = false;                // msckf_run_timed: k_root_gain notes when its sweep ends and when its update ends
-    // tracks that span more than WIDE_SPAN clone slots are sorted behind the others ([0, Fb) short, [Fb, F) long) and split
-    int Fb = 0, Fw = 0, Fw1 = 0, Mmax_band = 0, Mmax_wide = 0, Mmax_w1 = 0;   // (Fw1 of the Fw wide tracks have <= 15 views)
-    // Round 5: a long track (more than WIDE_SPAN clone slots) is SPLIT (k_feature.h, two-level nullspace basis): the sorted
-    // arrays hold its blocks behind the F tracks -- [F, F + nNarrow) the narrow blocks of its view groups (ordinary <= 10-slot
-    // tracks to every K5 kernel, sorted by (first slot, last slot) among themselves), [F + nNarrow, Fs) one remainder block per
-    // long track (3 (groups - 1) rows that touch every slot of the track).  The long tracks themselves, [Fb, F), are entries
-    // of K1-K3 only (gate, mask, counters): no K5 plan names them.
-    int Fs = 0, nNarrow = 0;              // entries of the sorted arrays; narrow blocks
-    int sumMs = 0;                        // views of all entries
-    bool split_on = false;                // this batch's long tracks were split (Fw > 0: k_feature<64, true> writes their blocks)
-    std::vector<SplitRec> h_split;        // per long track, in sorted order
-    std::vector<int> h_parent;            // [Fs - F] sorted index of the long track a block belongs to
+    // Round 5: a long track (more than WIDE_SPAN clone slots) is SPLIT (k_feature.h, two-level nullspace basis; batch_order.h:
+    // its blocks sit behind the F tracks in the sorted arrays)
     Buf dSplit, dRem;
-    int rem_cap = 0;                      // rows the remainder blocks may hold in all (3 per view group)
     // remainder rows (capacity: 3 per view group) up to which K6-K7 takes them as they are (msckf_debug_set_rem_direct_rows).  Measured
     // on tracks ~ U[2, 30] at N = 30, as they are against their own (cut) merge tree: 450 tracks 777 / 971 us, 600 (3100 rows)
     // 961 / 1056, 800 (4250 rows) 1221 / 1185, 1000 1486 / 1286
@@ -651,17 +638,29 @@ void invalidate_batch(msckf_ctx* c) {
 // planned for this context alone: their narrow blocks are ordinary tracks of the 60-column band pipeline, their remainder
 // blocks a small dense QR beside it.  Any window size, both dtypes.  Under the group exchange of a sharded update only with
 // split records (msckf_set_exchange_split: the remainder rows ride in the record); never where a plan is forced.
-constexpr int WIDE_SPAN = SPLIT_GSLOTS;
+// (which tracks those are, and how they are cut: batch_order.h)
+static_assert(kOrderOk == MSCKF_OK && kOrderErrArg == MSCKF_ERR_ARG && kOrderErrDupSlot == MSCKF_ERR_DUP_SLOT, "batch_order.h returns the ABI's codes");
 // the sequential block update (k_gstream.h) on DENSE rows at this window size: strips and LDS
-bool gstream_ok_dc(const msckf_ctx* c, int dc) {
-    if (!c->gs_enabled || dc < 1) return false;
+bool gstream_fits(int dc) {
     const int nb = (dc + 15) / 16, ns = nb + 1;
     return ns <= GS_MAX_NS && gstream_lds_doubles(ns, nb) * 8 <= (size_t)(LDS_MAX_BYTES - 1024);
 }
-bool split_ok(const msckf_ctx* c, int N) {
-    if ((c->cfg.flags & (MSCKF_FLAG_TREE_PLAN | MSCKF_FLAG_BAND_ONLY)) || (c->xchg && c->xsplit_rows == 0)) return false;
+bool gstream_ok_dc(const msckf_ctx* c, int dc) { return c->gs_enabled && dc >= 1 && gstream_fits(dc); }
+bool split_switch() {                     // MSCKF_SPLIT=0: no track is split
     static const bool off = [] { const char* e = std::getenv("MSCKF_SPLIT"); return e && std::atoi(e) == 0; }();
-    return !off && N > WIDE_SPAN && gstream_ok_dc(c, 6 * N);
+    return !off;
+}
+// the split of long tracks as far as the context decides it (c may be null: msckf_exchange_split_rule's defaults)
+bool split_possible(const msckf_ctx* c, int N) {
+    if (c && (c->cfg.flags & (MSCKF_FLAG_TREE_PLAN | MSCKF_FLAG_BAND_ONLY))) return false;
+    return split_switch() && N > WIDE_SPAN && (c ? gstream_ok_dc(c, 6 * N) : gstream_fits(6 * N));
+}
+inline bool split_records(const msckf_ctx* c) { return c->xchg && c->xsplit_rows > 0; }      // msckf_set_exchange_split is in force
+bool split_ok(const msckf_ctx* c, int N) { return !(c->xchg && c->xsplit_rows == 0) && split_possible(c, N); }
+// remainder rows up to which K6-K7 takes them as they are at this window size
+int rem_direct_cap(const msckf_ctx* c, int dc) {
+    if (!c) return dc > FOLD_RLDS_MAX_W ? 16 * GS_MAX_NB2 : msckf_ctx::REM_DIRECT_DEFAULT;
+    return dc > FOLD_RLDS_MAX_W ? c->rem_direct_max_wide : c->rem_direct_max;
 }
 struct Run { int b, e; };                 // entries [b, e) of the sorted arrays
 
@@ -677,7 +676,7 @@ void build_tree(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
     const int N = c->N;
     const int leaf_rows = c->cfg.leaf_rows > 0 ? c->cfg.leaf_rows : leaf_rows_default;
     const int arity = c->cfg.merge_arity > 0 ? c->cfg.merge_arity : 6;
-    const int rem0 = c->split_on ? c->F + c->nNarrow : (1 << 30);        // remainder blocks: entries [rem0, Fs)
+    const int rem0 = c->ord.split_on ? c->F + c->ord.nNarrow : (1 << 30);        // remainder blocks: entries [rem0, Fs)
     nodes.clear();
     levels.clear();
     size_t off = off0;
@@ -705,7 +704,7 @@ void build_tree(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
                 if (live(e)) {
                     // (rows of the entry: at most 2 per view; a remainder block holds 3 (groups - 1) of them unless the track's geometry
                     //  is degenerate -- an estimate is all a leaf's size needs, k_fold takes what it finds in register batches of 256)
-                    const int r = e >= rem0 ? 3 * ((int)c->h_split[c->h_parent[e - c->F] - c->Fb].ng - 1) : 2 * (view_sorted[e + 1] - view_sorted[e]);
+                    const int r = e >= rem0 ? 3 * ((int)c->ord.h_split[c->ord.h_parent[e - c->F] - c->ord.Fb].ng - 1) : 2 * (view_sorted[e + 1] - view_sorted[e]);
                     if (e > f && rows + r > leaf_rows) break;
                     rows += r;
                     lo = std::min(lo, fmin[e]);
@@ -845,7 +844,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
     }
     c->leaf_narrow = c->leaf_wide = false;
     // leaves that may ride in the root's launch (k_leaf_root_gain): their rows whole cache lines of 64 doubles, 16-double aligned
-    const bool leaf_cand = c->leaf_stream_enabled && c->stream_enabled && mode == 0 && !c->xchg && !c->split_on && runs.size() == 1 &&
+    const bool leaf_cand = c->leaf_stream_enabled && c->stream_enabled && mode == 0 && !c->xchg && !c->ord.split_on && runs.size() == 1 &&
                            6 * max_span + 1 <= 64 && c->leaf_nf == SWEEP_NW && !c->leaf_tall;
     c->leaf_ld64 = leaf_cand;
     c->leaf_fused = false;
@@ -861,7 +860,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
     const bool xchg = c->xchg;
     // k_sweep form, no export record, no split long tracks: the root block and the zero words head the workspace, where they
     // stay from plan to plan (msckf_ctx::ws_head); the leaves' and the merges' blocks, which move with the leaf counts, behind them
-    const bool head = mode == 0 && !xchg && !c->split_on && runs.size() == 1;
+    const bool head = mode == 0 && !xchg && !c->ord.split_on && runs.size() == 1;
     const size_t head_zero = ((size_t)dc * (dc + 1) + 15) & ~(size_t)15;
     size_t off = xchg ? rec_head(c) + (size_t)N * XCHG_SLOT + rec_rem_doubles(c) : head ? head_zero + 16 : 0;
     if (xchg) c->h_xflags.assign(N, 0.0);
@@ -1061,14 +1060,14 @@ void plan_batch(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
     c->wide_active = false;
     c->ws_head = false;
     c->rnodes.clear(); c->rlevels.clear(); c->rroot = -1; c->rroot_off = 0; c->rtops.clear(); c->rtop_rows = 0;
-    const int F = c->F, Fs = c->Fs;
+    const int F = c->F, Fs = c->ord.Fs;
     // a block is as valid as the track it was split off
     std::vector<unsigned char> vfull;
     const std::vector<unsigned char>* valid = valid_in;
     if (valid_in && Fs > F) {
         vfull.assign(valid_in->begin(), valid_in->begin() + F);
         vfull.resize(Fs);
-        for (int i = F; i < Fs; ++i) vfull[i] = (*valid_in)[c->h_parent[i - F]];
+        for (int i = F; i < Fs; ++i) vfull[i] = (*valid_in)[c->ord.h_parent[i - F]];
         valid = &vfull;
     }
     auto tree_only = [&](const std::vector<Run>& runs) {
@@ -1080,9 +1079,9 @@ void plan_batch(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
         c->rbuf_doubles = off_end;
         c->root_band = c->dc;                                             // a dense triangle
     };
-    if (c->split_on) {
+    if (c->ord.split_on) {
         // (three runs, each sorted by first slot on its own: a leaf's rows must come sorted by their first column)
-        const std::vector<Run> band_runs{{0, c->Fb}, {F, F + c->nNarrow}}, all_runs{{0, c->Fb}, {F, F + c->nNarrow}, {F + c->nNarrow, Fs}};
+        const std::vector<Run> band_runs{{0, c->ord.Fb}, {F, F + c->ord.nNarrow}}, all_runs{{0, c->ord.Fb}, {F, F + c->ord.nNarrow}, {F + c->ord.nNarrow, Fs}};
         if (!c->no_wide && build_plan_band(c, fmin, fmax, view_sorted, valid, band_runs)) {
             c->band_plan = true; c->wide_active = true;
             // the remainder blocks: taken by K6-K7 as they are when they are few (rem_direct), else a merge tree of their own
@@ -1093,7 +1092,7 @@ void plan_batch(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
             //  ~ U[2, 30], 5850 rows, leaves of 96 / 128 / 160 / 176 / 192 / 208 / 256 rows: 2149 / 2151 / 2113 / 2097 / 1940 / 2164 /
             //  2175 us per update; by the 3-per-group bound, i.e. two batches per leaf, 2160; leaves of 1024 rows with merges of up
             //  to six triangles 2415)
-            build_tree(c, fmin, fmax, view_sorted, valid, {{F + c->nNarrow, Fs}}, c->rbuf_doubles, c->rnodes, c->rlevels, c->rroot,
+            build_tree(c, fmin, fmax, view_sorted, valid, {{F + c->ord.nNarrow, Fs}}, c->rbuf_doubles, c->rnodes, c->rlevels, c->rroot,
                        c->rroot_off, off_end, nl, c->rem_leaf_rows > 0 ? c->rem_leaf_rows : (c->dc > FOLD_RLDS_MAX_W ? 512 : fold_bmax(c->dc)), false,
                        c->rem_cut_rows >= 0 ? c->rem_cut_rows : (c->dc > FOLD_RLDS_MAX_W ? 0 : 600), &c->rtops);
             for (int k : c->rtops) c->rtop_rows += c->rnodes[k].w;
@@ -1132,7 +1131,7 @@ int launch_fold_levels(msckf_ctx* c, const std::vector<std::pair<int, int>>& lev
             const FoldNode& n = all_nodes[i];
             maxw = std::max(maxw, n.w);
             if (n.kind == 0) {
-                const int rows = 2 * (c->h_view_sorted[n.src_end] - c->h_view_sorted[n.src_begin]);
+                const int rows = 2 * (c->ord.h_view[n.src_end] - c->ord.h_view[n.src_begin]);
                 leaf_rows_max = std::max(leaf_rows_max, rows);
             } else {
                 leaf_rows_max = 1 << 30;
@@ -1183,7 +1182,7 @@ LSweepArgs lsweep_args(msckf_ctx* c, int node_base) {
     a.rank = ptr<int>(c->dRank);
     a.accepted = ptr<unsigned char>(c->dAcc);
     a.rbuf = ptr<double>(c->dRbuf);
-    a.zero_idx = c->stack_elems;
+    a.zero_idx = c->ord.stack_elems;
     a.ld64 = c->leaf_ld64 ? 1 : 0;
     return a;
 }
@@ -1360,9 +1359,9 @@ int launch_feature(msckf_ctx* c) {
     a.rank = ptr<int>(c->dRank); a.accepted = ptr<unsigned char>(c->dAcc); a.gamma = ptr<double>(c->dGamma);
     a.select = c->use_select ? ptr<unsigned char>(c->dSelFlags) : nullptr;
     a.stamps = c->dStamps.p ? ptr<long long>(c->dStamps) + 8 * 8192 : nullptr;   // behind the fold stamps
-    a.zero_idx = c->stack_elems;
+    a.zero_idx = c->ord.stack_elems;
     c->gate_direct = c->want_direct && !c->use_select;      // (long tracks: k_feature<64, true> mirrors its track's results as well)
-    if (c->gate_direct) { a.rank_h = static_cast<int*>(c->hGate); a.acc_h = static_cast<unsigned char*>(c->hGate) + (size_t)c->Fs * 4; }
+    if (c->gate_direct) { a.rank_h = static_cast<int*>(c->hGate); a.acc_h = static_cast<unsigned char*>(c->hGate) + (size_t)c->ord.Fs * 4; }
     // one launch per class of tracks: the short tracks [0, Fb) and the long ones [Fb, F), which are split (k_feature<64, true>
     // writes their narrow and remainder blocks)
     hipStream_t st = c->stream;
@@ -1390,7 +1389,7 @@ int launch_feature(msckf_ctx* c) {
         else hipLaunchKernelGGL((k_feature<64, true>), dim3(nf), dim3(64), (size_t)lds_d * 8, st, a);
         if (c->rem_direct) {             // few remainder rows: one dense matrix for K6-K7, no QR of their own
             RemScatterArgs r{};
-            r.split = ptr<SplitRec>(c->dSplit); r.n_tracks = nf; r.rows_cap = c->rem_cap;
+            r.split = ptr<SplitRec>(c->dSplit); r.n_tracks = nf; r.rows_cap = c->ord.rem_cap;
             r.dc = c->dc; r.N = c->N;
             r.view_ptr = a.view_ptr; r.obs_slot = a.obs_slot; r.blk_off = a.blk_off; r.stack = a.stack; r.stack_f32 = a.stack_f32;
             r.rank = a.rank; r.accepted = a.accepted; r.out = rem_rows(c); r.nrows = rem_count(c);
@@ -1398,22 +1397,22 @@ int launch_feature(msckf_ctx* c) {
         }
     };
     c->wide_on_stream2 = false;
-    if (c->split_on && c->Fw > 0) {
+    if (c->ord.split_on && c->ord.Fw > 0) {
         // a long track's kernel is ONE wavefront's latency per track (~6 us per view: 190 us at 30 views) however few they are: it
         // runs on the second stream beside the short tracks' launch; the leaves wait for both (ev_wfeat, run_pipeline)
         if (c->wide_concurrent) {
             HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
             HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
             st = c->stream2;
-            go_split(c->Fb, c->Fw, c->Mmax_wide);
+            go_split(c->ord.Fb, c->ord.Fw, c->ord.Mmax_wide);
             HIPCHK(c, hipEventRecord(c->ev_wfeat, c->stream2));
             c->wide_on_stream2 = true;
             st = c->stream;
-            go(0, c->Fb, c->Mmax_band);
+            go(0, c->ord.Fb, c->ord.Mmax_band);
         } else {
-            go(0, c->Fb, c->Mmax_band); go_split(c->Fb, c->Fw, c->Mmax_wide);
+            go(0, c->ord.Fb, c->ord.Mmax_band); go_split(c->ord.Fb, c->ord.Fw, c->ord.Mmax_wide);
         }
-    } else go(0, c->F, c->Mmax);
+    } else go(0, c->F, c->ord.Mmax);
     HIPCHK(c, hipGetLastError());
     return MSCKF_OK;
 }
@@ -1843,7 +1842,7 @@ int launch_root_and_gain_w(msckf_ctx* c, int node, int nsteps, int rc_log2, cons
 int gate_counts(msckf_ctx* c, int out[4], std::vector<unsigned char>* acc_sorted, bool copied = false) {
     out[0] = out[1] = out[2] = out[3] = 0;
     if (c->F == 0) return MSCKF_OK;
-    const size_t F = c->F, Fs = c->Fs;          // (the blocks of split long tracks sit behind the F tracks: not counted)
+    const size_t F = c->F, Fs = c->ord.Fs;          // (the blocks of split long tracks sit behind the F tracks: not counted)
     if (!copied) {
         HIPCHK(c, hipMemcpyAsync(c->hGate, c->dGateArena.p, Fs * 5, hipMemcpyDeviceToHost, c->stream));   // rank | accepted
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1851,7 +1850,7 @@ int gate_counts(msckf_ctx* c, int out[4], std::vector<unsigned char>* acc_sorted
     const int* rk = static_cast<const int*>(c->hGate);
     const unsigned char* acc = static_cast<const unsigned char*>(c->hGate) + Fs * 4;
     for (int s = 0; s < c->F; ++s) {
-        if (acc[s] == 1) { out[0]++; out[1] += 2 * (c->h_view_sorted[s + 1] - c->h_view_sorted[s]) - rk[s]; }
+        if (acc[s] == 1) { out[0]++; out[1] += 2 * (c->ord.h_view[s + 1] - c->ord.h_view[s]) - rk[s]; }
         else if (acc[s] == 2) out[2]++;
         else if (acc[s] == 3) out[3]++;
     }
@@ -1941,9 +1940,9 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     src.first = c->root >= 0 ? root_block(c) : nullptr; src.band = c->root_band;
     src.mirror = rec.direct ? c->hRes : nullptr;
     src.two_sources_in_batch = c->wide_active;
-    if (direct) { src.second = rem_rows(c); src.nb2 = (c->rem_cap + 15) / 16; src.nb2_dev = rem_count(c); }
+    if (direct) { src.second = rem_rows(c); src.nb2 = (c->ord.rem_cap + 15) / 16; src.nb2_dev = rem_count(c); }
     // the dense remainder rows are applied by a launch of their own; the update on the band root starts from its P_out / dx
-    const bool t2_early = direct && with_gain && c->root >= 0 && gstream_ok(c, c->root_band) && (c->rem_cap + 15) / 16 >= t2_early_min();
+    const bool t2_early = direct && with_gain && c->root >= 0 && gstream_ok(c, c->root_band) && (c->ord.rem_cap + 15) / 16 >= t2_early_min();
     if (t2_early) {
         hipStream_t rs = c->wide_on_stream2 ? c->stream2 : c->stream;
         if ((rc = launch_gain_t2_early(c, src, rs)) != MSCKF_OK) return rc;
@@ -2063,8 +2062,7 @@ int tracks_ensure(msckf_ctx* c) {
 // the mirror freed rows, which may be handed out again: a loaded batch no longer writes refreshed points back
 inline void tracks_rows_freed(msckf_ctx* c, size_t n) { if (n > 0) c->batch_from_store = false; }
 
-int launch_track_emit(msckf_ctx* c, const TrackEmitSrc* src, int F, int sumM, const int32_t* view_ptr,
-                      const std::vector<int>& h_view, char* draw, size_t r_base, size_t r_m, size_t r_rho, size_t r_slot) {
+int launch_track_emit(msckf_ctx* c, const TrackEmitSrc* src, int F, int sumM, const int32_t* view_ptr, char* draw, const RawLayout& raw) {
     int rc = MSCKF_OK;
     auto E = [&](Buf& b, size_t bytes) { if (rc == MSCKF_OK) rc = ensure(c, b, bytes); };
     E(c->dLineBase, (size_t)sumM * 24); E(c->dLineDir, (size_t)sumM * 24); E(c->dLineConf, (size_t)sumM * 8);
@@ -2074,14 +2072,14 @@ int launch_track_emit(msckf_ctx* c, const TrackEmitSrc* src, int F, int sumM, co
     if (int rcs = stage_acquire(c, c->trk_load_stage, (size_t)F * sizeof(TrackEmitRec))) return rcs;
     TrackEmitRec* rec = static_cast<TrackEmitRec*>(c->trk_load_stage.p);
     for (int sidx = 0; sidx < F; ++sidx) {
-        const int f = c->perm[sidx];
-        rec[f] = TrackEmitRec{src->rows[f], view_ptr[f + 1] - view_ptr[f], view_ptr[f], h_view[sidx], sidx, src->lost[f], src->tracked[f], 0};
+        const int f = c->ord.perm[sidx];
+        rec[f] = TrackEmitRec{src->rows[f], view_ptr[f + 1] - view_ptr[f], view_ptr[f], c->ord.h_view[sidx], sidx, src->lost[f], src->tracked[f], 0};
     }
     TrackEmitArgs a{};
     a.s = c->trk; a.rec = rec; a.F = F; a.cam_t = ptr<double>(c->dCamT);
-    a.uv_raw = reinterpret_cast<double*>(draw); a.slot_raw = reinterpret_cast<int*>(draw + r_slot);
-    a.base_raw = reinterpret_cast<double*>(draw + r_base); a.m_raw = reinterpret_cast<double*>(draw + r_m);
-    a.rho_raw = reinterpret_cast<double*>(draw + r_rho);
+    a.uv_raw = reinterpret_cast<double*>(draw); a.slot_raw = reinterpret_cast<int*>(draw + raw.r_slot);
+    a.base_raw = reinterpret_cast<double*>(draw + raw.r_base); a.m_raw = reinterpret_cast<double*>(draw + raw.r_m);
+    a.rho_raw = reinterpret_cast<double*>(draw + raw.r_rho);
     a.line_base = ptr<double>(c->dLineBase); a.line_dir = ptr<double>(c->dLineDir); a.line_conf = ptr<double>(c->dLineConf);
     a.lost_for = ptr<int>(c->dLostFor); a.tracked_for = ptr<int>(c->dTrackedFor); a.row_sorted = ptr<int>(c->dTrkRowSorted);
     hipLaunchKernelGGL(k_track_emit, dim3((F + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
@@ -2433,10 +2431,10 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     c->no_wide = false;
     if (F == 0) {
         c->F = 0;
-        c->sumM = 0; c->Mmax = 0; c->nodes.clear(); c->levels.clear(); c->snodes.clear(); c->sfolds.clear(); c->sweep_levels.clear(); c->n_group_merges = 0;
-        c->band_plan = false; c->root = -1; c->perm.clear();
-        c->Fb = c->Fw = c->Fw1 = 0; c->wide_active = false;
-        c->Fs = 0; c->nNarrow = 0; c->sumMs = 0; c->split_on = false; c->rem_cap = 0; c->rem_direct = false; c->h_split.clear(); c->h_parent.clear();
+        c->sumM = 0; c->ord.reset(); c->nodes.clear(); c->levels.clear(); c->snodes.clear(); c->sfolds.clear(); c->sweep_levels.clear(); c->n_group_merges = 0;
+        c->band_plan = false; c->root = -1;
+        c->wide_active = false;
+        c->rem_direct = false;
         c->rnodes.clear(); c->rlevels.clear(); c->rroot = -1; c->rtops.clear(); c->rtop_rows = 0;
         c->plan_valid = false;
         c->xchg_planned = false;
@@ -2468,33 +2466,25 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
         if (M < 1 || M > c->maxM) return MSCKF_ERR_ARG;
     }
     const int sumM = view_ptr[F];
-    // raw image (input order): doubles first, then the ints
-    const size_t r_uv = 0, r_base = r_uv + (size_t)sumM * 16, r_m = r_base + (size_t)F * 24, r_rho = r_m + (size_t)F * 24;
-    const size_t r_slot = r_rho + (size_t)F * 8;
-    const size_t raw_bytes = (r_slot + (size_t)sumM * 4 + 15) & ~(size_t)15;
-    // the sort's records behind the arrays: one per entry of the sorted arrays -- the tracks and, for long tracks that are split,
-    // their blocks: a narrow block per view group of 2+ views and one remainder block, i.e. at most M / 2 + 1 per track (a
-    // ragged track may span 11+ slots with three views) -- and one SplitRec per long track
-    const size_t rec_cap = 2 * (size_t)F + (size_t)sumM / 2 + 8;
-    const size_t pin_bytes = raw_bytes + rec_cap * sizeof(GatherRec) + ((size_t)F + 1) * sizeof(SplitRec);
-    if (c->hFeatCap < pin_bytes) {
+    const RawLayout raw = raw_layout(F, sumM);           // (input order; the sort's records behind the arrays)
+    if (c->hFeatCap < raw.pin_bytes) {
         if (c->hFeat) HIPCHK(c, hipHostFree(c->hFeat));
         c->hFeat = nullptr; c->hFeatCap = 0;
-        HIPCHK(c, hipHostMalloc(&c->hFeat, pin_bytes + pin_bytes / 2));
-        c->hFeatCap = pin_bytes + pin_bytes / 2;
+        HIPCHK(c, hipHostMalloc(&c->hFeat, raw.pin_bytes + raw.pin_bytes / 2));
+        c->hFeatCap = raw.pin_bytes + raw.pin_bytes / 2;
     }
     // small batches: the small arrays reach HBM through a copy KERNEL reading the pinned image (k_stage) and k_gather reads the
     // sort's records from it (zero-copy) -- no copy command but the observations', none of the ~9 us each one waits behind its
     // predecessor; large ones: DMA, beside the host's sort (measured at 10000 tracks: zero-copy 620 us per call, DMA 578)
     static const int zc_max = [] { const char* e = std::getenv("MSCKF_ZEROCOPY_MAX"); return e ? std::atoi(e) : 4096; }();
     const bool zc = F <= zc_max;
-    if (int rca = ensure(c, c->dRawArena, pin_bytes)) return rca;
+    if (int rca = ensure(c, c->dRawArena, raw.pin_bytes)) return rca;
     char* hb = static_cast<char*>(c->hFeat);
     char* draw = static_cast<char*>(c->dRawArena.p);
     const bool par = c->pool && F >= host_par_min();
     if (!emit) {
-        if (par) c->pool->copy(hb + r_uv, obs_uv, (size_t)sumM * 16); else std::memcpy(hb + r_uv, obs_uv, (size_t)sumM * 16);
-        HIPCHK(c, hipMemcpyAsync(draw, hb + r_uv, (size_t)sumM * 16, hipMemcpyHostToDevice, c->stream));
+        if (par) c->pool->copy(hb + raw.r_uv, obs_uv, (size_t)sumM * 16); else std::memcpy(hb + raw.r_uv, obs_uv, (size_t)sumM * 16);
+        HIPCHK(c, hipMemcpyAsync(draw, hb + raw.r_uv, (size_t)sumM * 16, hipMemcpyHostToDevice, c->stream));
     }
     // (the one-shot call's state went up on the side stream: the main stream learns of it HERE, behind a copy it has to wait for
     //  anyway -- between k_gather and k_feature the cross-stream wait cost ~4 us of an otherwise back-to-back pair)
@@ -2504,218 +2494,84 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     // key = (class, first slot, last slot); class 0: tracks of up to WIDE_SPAN clone slots (and long ones that cannot be split:
     // views out of slot order, more than SPLIT_MAXG groups, more views than k_feature<64> holds); class 2: long tracks, split
     const bool split = split_ok(c, N);
-    const size_t NN = (size_t)N * N;
     std::vector<int> key_in(F);
     std::vector<unsigned char> M_in(F);
-    int Mmax = 0, Mmax_cls[3] = {0, 0, 0};
-    int n_mid = 0, n_long = 0;               // tracks of 11 - 15 slots / of more (any class)
+    ScanPart tot;
     {
         const int nch = par ? std::min(4 * (c->pool->workers() + 1), (F + 255) / 256) : 1;
-        std::vector<int> ch_err(nch, MSCKF_OK), ch_mmax(5 * nch, 0);
+        std::vector<ScanPart> part(nch);
         const int maxM = c->maxM;
         auto validate = [&](int ch) {
             const int f0 = (int)((long long)F * ch / nch), f1 = (int)((long long)F * (ch + 1) / nch);
             const int a0 = view_ptr[f0], a1 = view_ptr[f1];
             if (!emit) {
-                std::memcpy(hb + r_slot + (size_t)a0 * 4, obs_slot + a0, (size_t)(a1 - a0) * 4);
-                std::memcpy(hb + r_base + (size_t)f0 * 24, idp_base + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
-                std::memcpy(hb + r_m + (size_t)f0 * 24, idp_m + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
-                std::memcpy(hb + r_rho + (size_t)f0 * 8, idp_rho + f0, (size_t)(f1 - f0) * 8);
+                std::memcpy(hb + raw.r_slot + (size_t)a0 * 4, obs_slot + a0, (size_t)(a1 - a0) * 4);
+                std::memcpy(hb + raw.r_base + (size_t)f0 * 24, idp_base + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
+                std::memcpy(hb + raw.r_m + (size_t)f0 * 24, idp_m + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
+                std::memcpy(hb + raw.r_rho + (size_t)f0 * 8, idp_rho + f0, (size_t)(f1 - f0) * 8);
             }
-            int mm[3] = {0, 0, 0}, nmid = 0, nlong = 0;
-            for (int f = f0; f < f1; ++f) {
-                const int a = view_ptr[f], b = view_ptr[f + 1], M = b - a;
-                if (M < 1 || M > maxM) { ch_err[ch] = MSCKF_ERR_ARG; return; }
-                int lo = N, hi = -1;
-                bool ordered = true;
-                unsigned long long seen = 0;    // N <= 64 fast path; general check below
-                for (int i = a; i < b; ++i) {
-                    const int sl = obs_slot[i];
-                    if (sl < 0 || sl >= N) { ch_err[ch] = MSCKF_ERR_ARG; return; }
-                    if (sl < hi) ordered = false;
-                    lo = std::min(lo, sl); hi = std::max(hi, sl);
-                    if (N <= 64) {
-                        if (seen & (1ull << sl)) { ch_err[ch] = MSCKF_ERR_DUP_SLOT; return; }
-                        seen |= 1ull << sl;
-                    } else {
-                        for (int k = a; k < i; ++k) if (obs_slot[k] == sl) { ch_err[ch] = MSCKF_ERR_DUP_SLOT; return; }
-                    }
-                }
-                const int span = hi - lo + 1;
-                if (span > 15) ++nlong; else if (span > WIDE_SPAN) ++nmid;
-                const int cls = (split && span > WIDE_SPAN && ordered && M <= 31 && (span + SPLIT_GSLOTS - 1) / SPLIT_GSLOTS <= SPLIT_MAXG) ? 2 : 0;
-                key_in[f] = (int)(cls * NN + (size_t)lo * N + hi);
-                M_in[f] = (unsigned char)M;
-                mm[cls] = std::max(mm[cls], M);
-            }
-            for (int k = 0; k < 3; ++k) ch_mmax[5 * ch + k] = mm[k];
-            ch_mmax[5 * ch + 3] = nmid; ch_mmax[5 * ch + 4] = nlong;
+            part[ch] = scan_range(N, maxM, split, view_ptr, obs_slot, f0, f1, key_in.data(), M_in.data());
         };
         if (nch > 1) c->pool->run(nch, validate); else validate(0);
         for (int ch = 0; ch < nch; ++ch) {
-            if (ch_err[ch] != MSCKF_OK) { (void)hipStreamSynchronize(c->stream); return ch_err[ch]; }      // (the pinned image is in flight)
-            for (int k = 0; k < 3; ++k) Mmax_cls[k] = std::max(Mmax_cls[k], ch_mmax[5 * ch + k]);
-            n_mid += ch_mmax[5 * ch + 3]; n_long += ch_mmax[5 * ch + 4];
+            if (part[ch].err != kOrderOk) { (void)hipStreamSynchronize(c->stream); return part[ch].err; }      // (the pinned image is in flight)
+            tot.add(part[ch]);
         }
-        Mmax = std::max(Mmax_cls[0], std::max(Mmax_cls[1], Mmax_cls[2]));
     }
-    // A batch MOST of whose tracks span 11 - 15 slots and none more (BASELINE configs[4]: every track 15 views) keeps the
-    // 90-column band pipeline for all of them: split, each would leave 3 remainder rows to the dense tree
-    // ... and so does one whose remainder rows (6 per such track) would be too many for K6-K7 to take as they are: the 90-column
-    // pipeline (539 us at 2000 tracks ~ U[2, 15]) beats band pipeline + remainder tree (866 us) there
+    const int Mmax = tot.Mmax_all();
+    // mostly 11 - 15 slots and none more: the 90-column band pipeline for all of them (keeps_wide_tiles)
     // (not with split records: the whole batch's rule -- msckf_exchange_split_rule -- has decided that for every shard alike)
-    if (Mmax_cls[2] > 0 && n_long == 0 && !(c->xchg && c->xsplit_rows > 0) && (2 * n_mid > F || 6 * n_mid > (c->dc > FOLD_RLDS_MAX_W ? c->rem_direct_max_wide : std::min(c->rem_direct_max, 2048)))) {
-        for (int f = 0; f < F; ++f) key_in[f] = (int)((size_t)key_in[f] % NN);
-        Mmax_cls[0] = Mmax; Mmax_cls[2] = 0;
-    }
+    if (tot.Mmax[2] > 0 && !split_records(c) && keeps_wide_tiles(tot.n_mid, tot.n_long, F, rem_direct_cap(c, c->dc), c->dc > FOLD_RLDS_MAX_W))
+        drop_split_class(N, F, key_in.data(), tot);
     if (emit) {
         // (the store's floats never visit the host: k_track_emit lays the raw image down in front of k_gather, below)
-    } else if (!zc) HIPCHK(c, hipMemcpyAsync(draw + r_base, hb + r_base, raw_bytes - r_base, hipMemcpyHostToDevice, c->stream));
+    } else if (!zc) HIPCHK(c, hipMemcpyAsync(draw + raw.r_base, hb + raw.r_base, raw.raw_bytes - raw.r_base, hipMemcpyHostToDevice, c->stream));
     else {
-        const size_t n16 = (raw_bytes - r_base) / 16;           // (r_base and raw_bytes are multiples of 16)
+        const size_t n16 = (raw.raw_bytes - raw.r_base) / 16;           // (r_base and raw_bytes are multiples of 16)
         hipLaunchKernelGGL(k_stage, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, c->stream,
-                           reinterpret_cast<const uint4*>(hb + r_base), reinterpret_cast<uint4*>(draw + r_base), n16);
+                           reinterpret_cast<const uint4*>(hb + raw.r_base), reinterpret_cast<uint4*>(draw + raw.r_base), n16);
     }
     const double tv = now_us();
     if (c->n_chi2 <= 2 * Mmax) { (void)hipStreamSynchronize(c->stream); return MSCKF_ERR_ARG; }
-    c->F = F; c->sumM = sumM; c->Mmax = Mmax;            // validated: commit the batch size
-    // counting sort by the key: stable, O(F + N^2); the short tracks first, the long ones behind them
-    c->perm.resize(F);
-    std::vector<int> h_view, h_fmin(F), h_fmax(F);
-    long long blk = 0;
-    int Fs = F, sumMs = sumM;
-    GatherRec* rec = reinterpret_cast<GatherRec*>(hb + raw_bytes);
-    {
-        std::vector<int> cnt(3 * NN + 1, 0);
-        for (int f = 0; f < F; ++f) cnt[key_in[f] + 1]++;
-        // first / last slot of the sorted tracks: a run per occupied key
-        for (size_t k = 0, pos = 0; k < 3 * NN; ++k) {
-            const int n = cnt[k + 1];
-            if (n == 0) continue;
-            const int lo = (int)((k % NN) / N), hi = (int)(k % N);
-            std::fill(h_fmin.begin() + pos, h_fmin.begin() + pos + n, lo);
-            std::fill(h_fmax.begin() + pos, h_fmax.begin() + pos + n, hi);
-            pos += n;
-        }
-        for (size_t i = 1; i < cnt.size(); ++i) cnt[i] += cnt[i - 1];
-        c->Fb = cnt[NN];                                                  // short tracks: sorted positions [0, Fb)
-        c->Fw1 = 0;
-        c->Fw = F - c->Fb;                                                // long tracks, split: [Fb, F)
-        int* perm = c->perm.data();
-        for (int f = 0; f < F; ++f) perm[cnt[key_in[f]]++] = f;
-        c->Mmax_band = Mmax_cls[0]; c->Mmax_w1 = 0; c->Mmax_wide = Mmax_cls[2];
-        c->split_on = c->Fw > 0;
-        // ---- the blocks of the long tracks (k_feature.h): view groups of at most SPLIT_GSLOTS slots -> narrow blocks, one
-        //      remainder block per track
-        c->h_split.clear(); c->h_parent.clear();
-        struct Blk { int parent, f, a, M, lo, hi, pi, g; };
-        std::vector<Blk> narrow, wide;
-        int rem_cap = 0;
-        if (c->split_on) {
-            c->h_split.resize(c->Fw);
-            for (int sidx = c->Fb; sidx < F; ++sidx) {
-                const int f = perm[sidx], a = view_ptr[f], M = M_in[f], lo = h_fmin[sidx], hi = h_fmax[sidx];
-                const int span = hi - lo + 1, ng0 = (span + SPLIT_GSLOTS - 1) / SPLIT_GSLOTS, pi = sidx - c->Fb;
-                SplitRec sr{};
-                for (int g = 0; g < SPLIT_MAXG; ++g) sr.child[g] = -1;
-                int ng = 0, v = 0;
-                for (int g0 = 0; g0 < ng0; ++g0) {
-                    const int bnd = lo + (int)(((long long)(g0 + 1) * span) / ng0);       // slots [.., bnd): at most ceil(span / ng0) <= 10 of them
-                    const int v0 = v;
-                    while (v < M && obs_slot[a + v] < bnd) ++v;
-                    if (v == v0) continue;                                 // no view in this stretch of slots
-                    sr.gv[ng] = (unsigned char)v0;
-                    if (v - v0 >= 2) narrow.push_back({sidx, f, a + v0, v - v0, obs_slot[a + v0], obs_slot[a + v - 1], pi, ng});
-                    ++ng;
-                }
-                sr.gv[ng] = (unsigned char)M; sr.ng = (unsigned char)ng;
-                sr.rows_cap = 3 * ng; rem_cap += 3 * ng;
-                c->h_split[pi] = sr;
-                wide.push_back({sidx, f, a, M, lo, hi, pi, -1});
-            }
-            // the narrow blocks among themselves by (first slot, last slot): the band plan walks them as a second run
-            std::vector<int> cn(NN + 1, 0);
-            for (const Blk& b : narrow) cn[(size_t)b.lo * N + b.hi + 1]++;
-            for (size_t i = 1; i < cn.size(); ++i) cn[i] += cn[i - 1];
-            std::vector<Blk> sorted(narrow.size());
-            for (const Blk& b : narrow) sorted[cn[(size_t)b.lo * N + b.hi]++] = b;
-            narrow.swap(sorted);
-        }
-        c->nNarrow = (int)narrow.size();
-        if ((size_t)F + narrow.size() + wide.size() > rec_cap) { (void)hipStreamSynchronize(c->stream); c->last_error = "split: record capacity"; return MSCKF_ERR_STATE; }
-        c->rem_cap = rem_cap;
-        // (K6-K7 takes 16 dense rows in ~5 us; a merge tree over them is a leaf of ~100 us and ~170 us per level: the tree pays
-        //  beyond some 2000 rows)
-        // ... and the tree's kernels are at their slowest on windows wider than their LDS holds (N > 31: ~1 ms per level), where the
-        // rows are taken as they are up to four times as many
-        c->rem_direct = c->split_on && rem_cap <= (c->dc > FOLD_RLDS_MAX_W ? c->rem_direct_max_wide : c->rem_direct_max);
-        if (c->split_on && c->xchg && c->xsplit_rows > 0) {
-            // split records: the rows go to the record's remainder section, whose capacity every rank was told
-            if (rem_cap > c->xsplit_rows) {
-                (void)hipStreamSynchronize(c->stream);
-                c->last_error = "split records: the shard's remainder rows exceed msckf_set_exchange_split's capacity";
-                return MSCKF_ERR_ARG;
-            }
-            c->rem_direct = true;
-        }
-        Fs = F + (int)narrow.size() + (int)wide.size();
-        h_view.resize(Fs + 1); h_fmin.resize(Fs); h_fmax.resize(Fs);
-        c->h_parent.resize(Fs - F);
-        // the sorted CSR offsets and the offsets of the K4 blocks: a prefix over the sorted order; k_gather's records
-        int pos = 0;
-        for (int sidx = 0; sidx < F; ++sidx) {
-            const int f = perm[sidx], M = M_in[f];
-            h_view[sidx] = pos;
-            const bool parent = c->split_on && sidx >= c->Fb;              // (a split track has no block of its own)
-            rec[sidx] = GatherRec{f, view_ptr[f], M, pos, parent ? 0 : blk};
-            if (!parent) blk += (long long)(6 * M + 1) * (2 * M);
-            pos += M;
-        }
-        int e = F;
-        for (const Blk& b : narrow) {
-            h_view[e] = pos; h_fmin[e] = b.lo; h_fmax[e] = b.hi; c->h_parent[e - F] = b.parent;
-            rec[e] = GatherRec{b.f, b.a, b.M, pos, blk};
-            c->h_split[b.pi].child[b.g] = e;
-            blk += (long long)(6 * b.M + 1) * (2 * b.M);
-            pos += b.M; ++e;
-        }
-        for (const Blk& b : wide) {
-            h_view[e] = pos; h_fmin[e] = b.lo; h_fmax[e] = b.hi; c->h_parent[e - F] = b.parent;
-            rec[e] = GatherRec{b.f, b.a, b.M, pos, blk};
-            c->h_split[b.pi].wide = e;
-            blk += (long long)(6 * b.M + 1) * (3 * SPLIT_MAXG);
-            pos += b.M; ++e;
-        }
-        h_view[Fs] = pos;
-        sumMs = pos;
+    c->F = F; c->sumM = sumM;                            // validated: commit the batch size
+    // the pipeline's order (batch_order.h); k_gather's records go where it reads them.  A failure leaves `ord` invalid, as
+    // `have_features` says since the top of this call
+    BatchOrder& ord = c->ord;
+    const BatchOrder::Fail fail = ord.build(N, F, view_ptr, obs_slot, key_in.data(), M_in.data(), tot, raw.rec_cap,
+                                            split_records(c) ? c->xsplit_rows : -1, reinterpret_cast<GatherRec*>(hb + raw.raw_bytes));
+    if (fail != BatchOrder::kBuilt) {
+        (void)hipStreamSynchronize(c->stream);
+        if (fail == BatchOrder::kRecordCapacity) { c->last_error = "split: record capacity"; return MSCKF_ERR_STATE; }
+        c->last_error = "split records: the shard's remainder rows exceed msckf_set_exchange_split's capacity";
+        return MSCKF_ERR_ARG;
     }
-    c->Fs = Fs; c->sumMs = sumMs;
-    const size_t split_off = raw_bytes + (((size_t)Fs * sizeof(GatherRec) + 15) & ~(size_t)15);
-    if (c->split_on) std::memcpy(hb + split_off, c->h_split.data(), c->h_split.size() * sizeof(SplitRec));
-    c->h_view_sorted = h_view;
+    // (K6-K7 takes 16 dense rows in ~5 us; a merge tree over them is a leaf of ~100 us and ~170 us per level: the tree pays
+    //  beyond some 2000 rows)
+    // ... and the tree's kernels are at their slowest on windows wider than their LDS holds (N > 31: ~1 ms per level), where the
+    // rows are taken as they are up to four times as many
+    // (split records: the rows go to the record's remainder section, whose capacity every rank was told)
+    c->rem_direct = ord.split_on && (split_records(c) || ord.rem_cap <= rem_direct_cap(c, c->dc));
+    const int Fs = ord.Fs, sumMs = ord.sumMs;
+    const std::vector<int>&h_view = ord.h_view, &h_fmin = ord.h_fmin, &h_fmax = ord.h_fmax;
+    const size_t split_off = raw.split_off(Fs);
+    if (ord.split_on) std::memcpy(hb + split_off, ord.h_split.data(), ord.h_split.size() * sizeof(SplitRec));
     c->h_view_in.assign(view_ptr, view_ptr + F + 1);
-    c->h_fmin = h_fmin; c->h_fmax = h_fmax;
     const double ts = now_us(), t1 = ts;
 
     // sorted image (what the kernels read), written by k_gather: Fs entries, sumMs views
-    const size_t o_uv = 0, o_base = o_uv + (size_t)sumMs * 16, o_m = o_base + (size_t)Fs * 24, o_rho = o_m + (size_t)Fs * 24;
-    const size_t o_blk = o_rho + (size_t)Fs * 8, o_view = o_blk + (size_t)Fs * 8;
-    const size_t o_perm = o_view + (((size_t)(Fs + 1) * 4 + 7) & ~(size_t)7);                  // sorted position -> input index
-    const size_t o_slot = (o_perm + (size_t)Fs * 4 + 7) & ~(size_t)7, o_fmin = o_slot + (((size_t)sumMs * 4 + 7) & ~(size_t)7);
-    const size_t o_info = (o_fmin + (size_t)Fs * 4 + 15) & ~(size_t)15;                   // FeatInfo records (16-byte aligned)
-    const size_t feat_bytes = o_info + (size_t)Fs * sizeof(FeatInfo);
-    if (c->dFeatArena.bytes < feat_bytes && c->run_pending) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->run_pending = false; }
-    if (int rca = ensure(c, c->dFeatArena, feat_bytes)) return rca;
-    set_view(c->dObsUV, c->dFeatArena.p, o_uv, (size_t)sumMs * 16);
-    set_view(c->dBase, c->dFeatArena.p, o_base, (size_t)Fs * 24);
-    set_view(c->dMvec, c->dFeatArena.p, o_m, (size_t)Fs * 24);
-    set_view(c->dRho, c->dFeatArena.p, o_rho, (size_t)Fs * 8);
-    set_view(c->dBlkOff, c->dFeatArena.p, o_blk, (size_t)Fs * 8);
-    set_view(c->dViewPtr, c->dFeatArena.p, o_view, (size_t)(Fs + 1) * 4);
-    set_view(c->dObsSlot, c->dFeatArena.p, o_slot, (size_t)sumMs * 4);
-    set_view(c->dFmin, c->dFeatArena.p, o_fmin, (size_t)Fs * 4);
-    set_view(c->dFeatInfo, c->dFeatArena.p, o_info, (size_t)Fs * sizeof(FeatInfo));
-    set_view(c->dPerm, c->dFeatArena.p, o_perm, (size_t)Fs * 4);
+    const SortedLayout so = sorted_layout(Fs, sumMs, sizeof(FeatInfo));
+    if (c->dFeatArena.bytes < so.feat_bytes && c->run_pending) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->run_pending = false; }
+    if (int rca = ensure(c, c->dFeatArena, so.feat_bytes)) return rca;
+    set_view(c->dObsUV, c->dFeatArena.p, so.o_uv, (size_t)sumMs * 16);
+    set_view(c->dBase, c->dFeatArena.p, so.o_base, (size_t)Fs * 24);
+    set_view(c->dMvec, c->dFeatArena.p, so.o_m, (size_t)Fs * 24);
+    set_view(c->dRho, c->dFeatArena.p, so.o_rho, (size_t)Fs * 8);
+    set_view(c->dBlkOff, c->dFeatArena.p, so.o_blk, (size_t)Fs * 8);
+    set_view(c->dViewPtr, c->dFeatArena.p, so.o_view, (size_t)(Fs + 1) * 4);
+    set_view(c->dObsSlot, c->dFeatArena.p, so.o_slot, (size_t)sumMs * 4);
+    set_view(c->dFmin, c->dFeatArena.p, so.o_fmin, (size_t)Fs * 4);
+    set_view(c->dFeatInfo, c->dFeatArena.p, so.o_info, (size_t)Fs * sizeof(FeatInfo));
+    set_view(c->dPerm, c->dFeatArena.p, so.o_perm, (size_t)Fs * 4);
     // gate results: rank[Fs] (int) then accepted[Fs] (byte), contiguous so they come back in one copy
     if ((size_t)5 * Fs > c->dGateArena.bytes || (size_t)5 * Fs > c->hGateCap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2730,23 +2586,22 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     int rc = MSCKF_OK;
     auto E = [&](Buf& b, size_t bytes, bool z = false) { if (rc == MSCKF_OK) rc = ensure(c, b, bytes, z); };
     const size_t stack_es = c->cfg.dtype == MSCKF_DTYPE_F32 ? 4 : 8;
-    E(c->dStack, ((size_t)blk + 8) * stack_es); E(c->dGamma, (size_t)F * 8);
-    if (c->split_on) E(c->dSplit, c->h_split.size() * sizeof(SplitRec));
-    c->stack_elems = blk;
+    E(c->dStack, ((size_t)ord.stack_elems + 8) * stack_es); E(c->dGamma, (size_t)F * 8);
+    if (ord.split_on) E(c->dSplit, ord.h_split.size() * sizeof(SplitRec));
     if (rc != MSCKF_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     // the permutation on the device; in the one-shot call K1-K4 starts behind it while the host plans K5
-    if (!zc) HIPCHK(c, hipMemcpyAsync(draw + raw_bytes, hb + raw_bytes, (size_t)Fs * sizeof(GatherRec), hipMemcpyHostToDevice, c->stream));
-    if (c->split_on) HIPCHK(c, hipMemcpyAsync(c->dSplit.p, hb + split_off, c->h_split.size() * sizeof(SplitRec), hipMemcpyHostToDevice, c->stream));
+    if (!zc) HIPCHK(c, hipMemcpyAsync(draw + raw.raw_bytes, hb + raw.raw_bytes, (size_t)Fs * sizeof(GatherRec), hipMemcpyHostToDevice, c->stream));
+    if (ord.split_on) HIPCHK(c, hipMemcpyAsync(c->dSplit.p, hb + split_off, ord.h_split.size() * sizeof(SplitRec), hipMemcpyHostToDevice, c->stream));
     if (c->oneshot) HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
     if (emit) {
-        if (int rce = launch_track_emit(c, emit, F, sumM, view_ptr, h_view, draw, r_base, r_m, r_rho, r_slot)) return rce;
+        if (int rce = launch_track_emit(c, emit, F, sumM, view_ptr, draw, raw)) return rce;
     }
     {
         GatherArgs g;
         g.uv_in = reinterpret_cast<const double*>(draw);
-        g.slot_in = reinterpret_cast<const int*>(draw + r_slot); g.base_in = reinterpret_cast<const double*>(draw + r_base);
-        g.m_in = reinterpret_cast<const double*>(draw + r_m); g.rho_in = reinterpret_cast<const double*>(draw + r_rho);
-        g.rec = reinterpret_cast<const GatherRec*>((zc ? hb : draw) + raw_bytes);
+        g.slot_in = reinterpret_cast<const int*>(draw + raw.r_slot); g.base_in = reinterpret_cast<const double*>(draw + raw.r_base);
+        g.m_in = reinterpret_cast<const double*>(draw + raw.r_m); g.rho_in = reinterpret_cast<const double*>(draw + raw.r_rho);
+        g.rec = reinterpret_cast<const GatherRec*>((zc ? hb : draw) + raw.raw_bytes);
         g.uv = ptr<double>(c->dObsUV); g.base = ptr<double>(c->dBase); g.m = ptr<double>(c->dMvec); g.rho = ptr<double>(c->dRho);
         g.slot = ptr<int>(c->dObsSlot); g.fmin = ptr<int>(c->dFmin); g.view = ptr<int>(c->dViewPtr); g.perm = ptr<int>(c->dPerm);
         g.blk = ptr<long long>(c->dBlkOff); g.info = ptr<FeatInfo>(c->dFeatInfo);
@@ -2831,7 +2686,7 @@ static int replan_current(msckf_ctx* c, bool one_plan) {
     HIPCHK(c, hipStreamSynchronize(c->stream2));
     if (one_plan) c->no_wide = true;
     c->plan_valid = false;
-    plan_batch(c, c->h_fmin, c->h_fmax, c->h_view_sorted, nullptr);
+    plan_batch(c, c->ord.h_fmin, c->ord.h_fmax, c->ord.h_view, nullptr);
     c->plan_no_wide = true;                // (not a plan the cache may hand to the next batch)
     c->gather_off = c->rbuf_doubles;
     const size_t need = (c->rbuf_doubles + 16) * 8;
@@ -2924,7 +2779,7 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
     const size_t d = c->d;
     const RunRecord& r = c->last;
     // gate results and (when the gain stage ran) status | dx | P_out: two copies behind the pipeline, one sync
-    if (c->F > 0 && !c->gate_direct) HIPCHK(c, hipMemcpyAsync(c->hGate, c->dGateArena.p, (size_t)c->Fs * 5, hipMemcpyDeviceToHost, c->stream));
+    if (c->F > 0 && !c->gate_direct) HIPCHK(c, hipMemcpyAsync(c->hGate, c->dGateArena.p, (size_t)c->ord.Fs * 5, hipMemcpyDeviceToHost, c->stream));
     if (r.gain && !r.direct) {
         const size_t bytes = P_out ? c->res_p_off + d * d * 8 : c->res_dx_off + d * 8;
         HIPCHK(c, hipMemcpyAsync(c->hRes, c->dResArena.p, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2948,7 +2803,7 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
         // device can keep one out until the 0.5 s bound.  ONE retry on kernels that never wait inside a launch (separate merge
         // levels and root, round 3's K6-K7 launches), and the context stays on them.  Not with split long tracks in the batch
         // (their second source of rows needs the sequential block update), and not a merge (its rows are not this context's batch).
-        if (r.kind == RunKind::Pipeline && c->have_features && !c->split_on && !r.word1_ours && !c->retry_plain && c->gs_enabled) {
+        if (r.kind == RunKind::Pipeline && c->have_features && !c->ord.split_on && !r.word1_ours && !c->retry_plain && c->gs_enabled) {
             c->retry_plain = true;
             c->gs_enabled = false; c->stream_enabled = false;
             if (int r2 = replan_current(c, false)) return r2;
@@ -2960,7 +2815,7 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
     }
     const int rc = outcome_rc(c, o);
     if (accepted && c->F > 0 && !gate_done) {
-        for (int s = 0; s < c->F; ++s) accepted[c->perm[s]] = (acc_sorted[s] == 1) ? 1 : 0;
+        for (int s = 0; s < c->F; ++s) accepted[c->ord.perm[s]] = (acc_sorted[s] == 1) ? 1 : 0;
     }
     const char* hres = static_cast<const char*>(c->hRes);
     if (dx) {
@@ -3060,9 +2915,9 @@ int msckf_update(msckf_ctx* c, int32_t N, const double* P, const double* cam_R, 
         if (c->wide_on_stream2) HIPCHK(c, hipEventSynchronize(c->ev_wfeat));      // (the long tracks' results come from the second stream)
         const int Fn = c->F;
         const int* rk = static_cast<const int*>(c->hGate);
-        const unsigned char* acc = static_cast<const unsigned char*>(c->hGate) + (size_t)c->Fs * 4;
-        const int* perm = c->perm.data();
-        const int* hv = c->h_view_sorted.data();
+        const unsigned char* acc = static_cast<const unsigned char*>(c->hGate) + (size_t)c->ord.Fs * 4;
+        const int* perm = c->ord.perm.data();
+        const int* hv = c->ord.h_view.data();
         int cnt[4] = {0, 0, 0, 0};
         for (int s = 0; s < Fn; ++s) {
             const unsigned char a = acc[s];
@@ -3113,8 +2968,8 @@ int msckf_set_tracks(msckf_ctx* c, const double* line_base, const double* line_d
     std::vector<double> hb((size_t)sumM * 3), hd((size_t)sumM * 3), hc(sumM);
     std::vector<int> hl(F), ht(F);
     for (int sidx = 0; sidx < F; ++sidx) {                 // same permutation as set_features
-        const int f = c->perm[sidx];
-        const int a = c->h_view_in[f], M = c->h_view_in[f + 1] - a, pos = c->h_view_sorted[sidx];
+        const int f = c->ord.perm[sidx];
+        const int a = c->h_view_in[f], M = c->h_view_in[f + 1] - a, pos = c->ord.h_view[sidx];
         std::memcpy(&hb[(size_t)pos * 3], &line_base[(size_t)a * 3], (size_t)M * 24);
         std::memcpy(&hd[(size_t)pos * 3], &line_dir[(size_t)a * 3], (size_t)M * 24);
         std::memcpy(&hc[pos], &line_conf[a], (size_t)M * 8);
@@ -3177,7 +3032,7 @@ int msckf_replan(msckf_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(flags.data(), c->dSelFlags.p, c->F, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->plan_valid = false;                 // the plan no longer covers every candidate: the next upload plans afresh
-    plan_batch(c, c->h_fmin, c->h_fmax, c->h_view_sorted, &flags);
+    plan_batch(c, c->ord.h_fmin, c->ord.h_fmax, c->ord.h_view, &flags);
     c->gather_off = c->rbuf_doubles;
     // the blocks moved inside the R workspace: entries below their diagonals must read as zero again
     {
@@ -3233,7 +3088,7 @@ int msckf_get_selection(msckf_ctx* c, uint8_t* flags, double* idp_m, double* idp
     HIPCHK(c, hipMemcpyAsync(hw.data(), c->dWorld.p, (size_t)F * 24, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int s = 0; s < F; ++s) {
-        const int f = c->perm[s];
+        const int f = c->ord.perm[s];
         if (flags) flags[f] = hf[s];
         if (idp_rho) idp_rho[f] = hr[s];
         if (idp_m) std::memcpy(&idp_m[(size_t)f * 3], &hm[(size_t)s * 3], 24);
@@ -3262,7 +3117,7 @@ int msckf_run_associate(msckf_ctx* c, const msckf_assoc_params* ap, const double
     a.thr_epipolar = ap->epipolar_threshold; a.thr_homography = ap->homography_threshold;
     // matched keypoints in sorted feature order; results come back through the same permutation
     std::vector<double> muv((size_t)F * 2);
-    for (int s = 0; s < F; ++s) { muv[2 * s] = matched_uv[2 * c->perm[s]]; muv[2 * s + 1] = matched_uv[2 * c->perm[s] + 1]; }
+    for (int s = 0; s < F; ++s) { muv[2 * s] = matched_uv[2 * c->ord.perm[s]]; muv[2 * s + 1] = matched_uv[2 * c->ord.perm[s] + 1]; }
     int rc = MSCKF_OK;
     auto E = [&](Buf& b, size_t bytes) { if (rc == MSCKF_OK) rc = ensure(c, b, bytes); };
     E(c->dAssocUV, (size_t)F * 16); E(c->dAssocRes, (size_t)F * 8);
@@ -3278,8 +3133,8 @@ int msckf_run_associate(msckf_ctx* c, const msckf_assoc_params* ap, const double
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int* fv = reinterpret_cast<const int*>(back.data());
     for (int s = 0; s < F; ++s) {
-        result[c->perm[s]] = back[(size_t)F * 4 + s];
-        if (fail_view) fail_view[c->perm[s]] = fv[s];
+        result[c->ord.perm[s]] = back[(size_t)F * 4 + s];
+        if (fail_view) fail_view[c->ord.perm[s]] = fv[s];
     }
     return MSCKF_OK;
 }
@@ -4033,47 +3888,32 @@ int msckf_exchange_split_rule(const msckf_ctx* c, int32_t N, int32_t F, const in
     for (int i = 0; F > 0 && i < view_ptr[F]; ++i) if (obs_slot[i] < 0 || obs_slot[i] >= N) return MSCKF_ERR_ARG;
     out[0] = out[1] = out[2] = out[3] = 0;
     const int dc = 6 * N;
-    bool can = N > WIDE_SPAN;
-    if (c) can = can && !(c->cfg.flags & (MSCKF_FLAG_TREE_PLAN | MSCKF_FLAG_BAND_ONLY)) && gstream_ok_dc(c, dc);
-    else {
-        const int nb = (dc + 15) / 16, ns = nb + 1;
-        can = can && ns <= GS_MAX_NS && gstream_lds_doubles(ns, nb) * 8 <= (size_t)(LDS_MAX_BYTES - 1024);
-    }
-    {
-        static const bool off = [] { const char* e = std::getenv("MSCKF_SPLIT"); return e && std::atoi(e) == 0; }();
-        can = can && !off;
-    }
-    const int direct_max = c ? (dc > FOLD_RLDS_MAX_W ? c->rem_direct_max_wide : c->rem_direct_max)
-                             : (dc > FOLD_RLDS_MAX_W ? 16 * GS_MAX_NB2 : msckf_ctx::REM_DIRECT_DEFAULT);
-    // per track: span, and for a long one its view groups (as msckf_set_features cuts them)
+    const bool can = split_possible(c, N);
+    const int direct_max = rem_direct_cap(c, dc);
+    // per track: span, and for a long one its view groups (batch_order.h: as msckf_set_features cuts them)
     int n_mid = 0, n_long = 0, n_split = 0, max_span = 0, band_span = 0;
     bool all_split = true;
     std::vector<long long> rows(n_shards, 0);
     std::vector<int> first_slots;                         // (per track: the first slots of what the band plan will see)
     std::vector<int> fs_ptr(1, 0);
     for (int f = 0; f < F; ++f) {
-        const int a = view_ptr[f], b = view_ptr[f + 1], M = b - a;
-        int lo = N, hi = -1;
-        bool ordered = true;
-        for (int i = a; i < b; ++i) { if (obs_slot[i] < hi) ordered = false; lo = std::min(lo, obs_slot[i]); hi = std::max(hi, obs_slot[i]); }
-        const int span = hi - lo + 1, ng0 = (span + SPLIT_GSLOTS - 1) / SPLIT_GSLOTS;
+        const int32_t* slots = obs_slot + view_ptr[f];
+        const int M = view_ptr[f + 1] - view_ptr[f];
+        const TrackExtent e = track_extent(slots, M, N);
+        const int span = e.span();
         max_span = std::max(max_span, span);
-        if (span > 15) ++n_long; else if (span > WIDE_SPAN) ++n_mid;
-        if (span <= WIDE_SPAN) { band_span = std::max(band_span, span); first_slots.push_back(lo); fs_ptr.push_back((int)first_slots.size()); continue; }
-        if (!(ordered && M <= 31 && ng0 <= SPLIT_MAXG)) { all_split = false; first_slots.push_back(lo); fs_ptr.push_back((int)first_slots.size()); continue; }
-        ++n_split;
-        int ng = 0, v = 0;
-        for (int g0 = 0; g0 < ng0; ++g0) {
-            const int bnd = lo + (int)(((long long)(g0 + 1) * span) / ng0);
-            const int v0 = v;
-            while (v < M && obs_slot[a + v] < bnd) ++v;
-            if (v == v0) continue;
-            if (v - v0 >= 2) {                            // a narrow block: an ordinary track of the band plan
-                first_slots.push_back(obs_slot[a + v0]);
-                band_span = std::max(band_span, obs_slot[a + v - 1] - obs_slot[a + v0] + 1);
-            }
-            ++ng;
+        if (span > TILE_SPAN) ++n_long; else if (span > WIDE_SPAN) ++n_mid;
+        if (span <= WIDE_SPAN || !splittable(e, M)) {
+            if (span <= WIDE_SPAN) band_span = std::max(band_span, span); else all_split = false;
+            first_slots.push_back(e.lo); fs_ptr.push_back((int)first_slots.size());
+            continue;
         }
+        ++n_split;
+        const int ng = for_each_group(e.lo, span, slots, M, [&](int, int v0, int v1) {
+            if (v1 - v0 < 2) return;
+            first_slots.push_back(slots[v0]);             // a narrow block: an ordinary track of the band plan
+            band_span = std::max(band_span, slots[v1 - 1] - slots[v0] + 1);
+        });
         fs_ptr.push_back((int)first_slots.size());
         int r = 0;
         while (r + 1 < n_shards && f >= bounds[r + 1]) ++r;
@@ -4083,7 +3923,7 @@ int msckf_exchange_split_rule(const msckf_ctx* c, int32_t N, int32_t F, const in
     for (int r = 0; r < n_shards; ++r) { cap = std::max(cap, rows[r]); total += rows[r]; }
     bool split = can && n_split > 0 && all_split;
     // (a batch MOST of whose tracks span 11 - 15 slots and none more keeps the 90-column pipeline, as in msckf_set_features)
-    if (split && n_long == 0 && (2 * n_mid > F || 6 * n_mid > (dc > FOLD_RLDS_MAX_W ? direct_max : std::min(direct_max, 2048)))) split = false;
+    if (split && keeps_wide_tiles(n_mid, n_long, F, direct_max, dc > FOLD_RLDS_MAX_W)) split = false;
     if (split && total > direct_max) split = false;       // (no k_fold tree of the remainder rows on the merging rank)
     out[0] = split ? 1 : 0;
     out[1] = split ? band_span : max_span;
@@ -4094,11 +3934,7 @@ int msckf_exchange_split_rule(const msckf_ctx* c, int32_t N, int32_t F, const in
         for (int r = 0; r < n_shards; ++r)
             for (int f = bounds[r]; f < bounds[r + 1]; ++f) {
                 if (split) { for (int k = fs_ptr[f]; k < fs_ptr[f + 1]; ++k) flags[(size_t)r * N + first_slots[k]] = 1; }
-                else {
-                    int lo = N;
-                    for (int i = view_ptr[f]; i < view_ptr[f + 1]; ++i) lo = std::min(lo, obs_slot[i]);
-                    flags[(size_t)r * N + lo] = 1;
-                }
+                else flags[(size_t)r * N + track_extent(obs_slot + view_ptr[f], view_ptr[f + 1] - view_ptr[f], N).lo] = 1;
             }
     }
     return MSCKF_OK;
@@ -4580,9 +4416,9 @@ int msckf_debug_gate(msckf_ctx* c, double* gamma, int32_t* qdim) {
     HIPCHK(c, hipMemcpy(g.data(), c->dGamma.p, (size_t)c->F * 8, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(rk.data(), c->dRank.p, (size_t)c->F * 4, hipMemcpyDeviceToHost));
     for (int s = 0; s < c->F; ++s) {
-        const int f = c->perm[s];
+        const int f = c->ord.perm[s];
         if (gamma) gamma[f] = g[s];
-        if (qdim) qdim[f] = 2 * (c->h_view_sorted[s + 1] - c->h_view_sorted[s]) - rk[s];
+        if (qdim) qdim[f] = 2 * (c->ord.h_view[s + 1] - c->ord.h_view[s]) - rk[s];
     }
     return MSCKF_OK;
 }
@@ -4592,15 +4428,15 @@ int msckf_debug_gate_codes(msckf_ctx* c, uint8_t* codes, int32_t* n_blocks, uint
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->wide_on_stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
-    const int F = c->F, Fs = c->F > 0 ? c->Fs : 0;
+    const int F = c->F, Fs = c->F > 0 ? c->ord.Fs : 0;
     if (n_blocks) *n_blocks = Fs - F;
     if (F == 0) return MSCKF_OK;
     std::vector<unsigned char> a(Fs);
     HIPCHK(c, hipMemcpy(a.data(), c->dAcc.p, (size_t)Fs, hipMemcpyDeviceToHost));
-    if (codes) for (int s = 0; s < F; ++s) codes[c->perm[s]] = a[s];
+    if (codes) for (int s = 0; s < F; ++s) codes[c->ord.perm[s]] = a[s];
     for (int e = F; e < Fs; ++e) {
         if (block_codes) block_codes[e - F] = a[e];
-        if (block_track) block_track[e - F] = c->perm[c->h_parent[e - F]];
+        if (block_track) block_track[e - F] = c->ord.perm[c->ord.h_parent[e - F]];
     }
     return MSCKF_OK;
 }
@@ -4658,12 +4494,12 @@ int msckf_debug_compressed(msckf_ctx* c, double* T, double* rn) {
 int msckf_debug_split(msckf_ctx* c, int32_t out[8]) {
     if (!c || !out) return MSCKF_ERR_ARG;
     if (!c->have_features) return MSCKF_ERR_STATE;
-    out[0] = c->split_on ? c->Fw : 0;
-    out[1] = c->nNarrow;
-    out[2] = c->split_on ? c->rem_cap : 0;
+    out[0] = c->ord.split_on ? c->ord.Fw : 0;
+    out[1] = c->ord.nNarrow;
+    out[2] = c->ord.split_on ? c->ord.rem_cap : 0;
     out[3] = c->wide_active ? (c->rem_direct ? 1 : ((c->rroot >= 0 || !c->rtops.empty()) ? 2 : 0)) : 0;
     out[4] = (int)c->rlevels.size();
-    out[5] = c->Fs;
+    out[5] = c->ord.Fs;
     out[6] = c->band_plan ? 1 : 0;
     out[7] = c->band_plan ? c->sweep_mode : -1;
     return MSCKF_OK;

@@ -27,8 +27,8 @@ import numpy as np
 from msckf_amd import synth
 from oracle import msckf_oracle as oracle
 
-SPLIT_SLOTS = 10          # SPLIT_GSLOTS of csrc/k_feature.h: the widest view group of a split track
-SPLIT_SPAN = 15           # a track over more slots than this is split (up to it: 90-column band tiles)
+SPLIT_SLOTS = 10          # SPLIT_GSLOTS of csrc/batch_order.h: the widest view group of a split track
+SPLIT_SPAN = 15           # TILE_SPAN of csrc/batch_order.h: a track over more slots than this is split (up to it: 90-column band tiles)
 T2_EARLY_MIN = 20         # t2_early_min() of msckf_abi.hip: remainder row blocks from which they get a launch of their own
 
 # name: (clones of one half, tracks of one half, seed, p, c[, hole]).  What each is for is pinned by test_failing_batches.py.
@@ -100,7 +100,7 @@ def selected(prob, tracks):
 
 
 def view_groups(slots):
-    """The library's view groups of one track (msckf_set_features): ceil(span / 10) stretches, empty ones skipped."""
+    """The library's view groups of one track (for_each_group of csrc/batch_order.h): ceil(span / 10) stretches, empty ones skipped."""
     lo, hi = int(slots.min()), int(slots.max())
     span = hi - lo + 1
     ng0 = (span + SPLIT_SLOTS - 1) // SPLIT_SLOTS
@@ -127,8 +127,8 @@ def remainder_blocks(prob, split=None):
 
 
 # ---- gate matrices that are not SPD (gate byte 2) ----------------------------------------------------------------------
-WIDE_SPAN = 10            # WIDE_SPAN of msckf_abi.hip: a track over more slots is long (split when its views come in slot order)
-REM_DIRECT_MID = 2048     # remainder rows (6 per 11 - 15-slot track) up to which a batch without a longer track is still split
+WIDE_SPAN = 10            # WIDE_SPAN of csrc/batch_order.h: a track over more slots is long (split when its views come in slot order)
+REM_DIRECT_MID = 2048     # MID_DIRECT_ROWS of csrc/batch_order.h: remainder rows (6 per 11 - 15-slot track) up to which a batch without a longer track is still split
 
 # name: (N, F, M, seed, clone a, make_problem options, every track's views reversed,
 #        (shortest, longest track in views) -- the k_feature instance the batch's unsplit tracks reach:

@@ -99,3 +99,61 @@ def test_bad_arguments_are_refused():
     p = synth.make_problem(30, 50, 30, seed=13, variable_tracks=True, min_track=2)
     with pytest.raises(_ffi.EngineError):
         exchange_split_rule(p, [(0, 20), (20, 40)])          # the shards do not cover the batch
+
+
+def test_the_rule_and_the_shards_intake_agree():
+    """A sharded update is right only if the whole-batch rule on every rank and msckf_set_features on every shard cut the same
+    tracks the same way.  Both take their rules from csrc/batch_order.h; here the library's rule is held against what
+    batch_order_model.py derives from the BatchOrder of every shard (the model test_batch_order.py holds the header to), on the
+    random batches of that test that have no unsplittable long track, cut into two to four shards."""
+    import random
+    from types import SimpleNamespace
+    from batch_order_model import (RANDOM_N, REM_DIRECT_MID, SPLIT_SPAN, WIDE_SPAN, Order, batch, batch_lines, random_batches,
+                                   splittable, tracks)
+    n_split = n_whole = 0
+    for N in RANDOM_N:
+        rng = random.Random(2000 + N)
+        for b in random_batches(N, random.Random(1000 + N)):
+            trk = tracks(b)
+            F = len(trk)
+            span = [max(t) - min(t) + 1 for t in trk]
+            if F < 4 or any(s > WIDE_SPAN and not splittable(t) for s, t in zip(span, trk)):
+                continue
+            S = rng.randint(2, 4)
+            cuts = [0] + sorted(rng.sample(range(1, F), S - 1)) + [F]
+            shards = list(zip(cuts, cuts[1:]))
+            vp = np.asarray(b["view_ptr"], dtype=np.int32)
+            prob = SimpleNamespace(N=N, F=F, view_ptr=vp, obs_slot=np.asarray(b["obs_slot"], dtype=np.int32))
+            rule = exchange_split_rule(prob, shards)
+
+            def shard_orders(split):
+                out = []
+                for lo_f, hi_f in shards:
+                    o = Order()
+                    sub = batch(N, vp[lo_f:hi_f + 1] - vp[lo_f], b["obs_slot"][vp[lo_f]:vp[hi_f]], maxM=40, split=split, rem=1 << 20)
+                    assert batch_lines(sub, o)[3] == "build 0"
+                    out.append((o, hi_f - lo_f))
+                return out
+            # the whole batch's decision (library defaults): the window must fit K6-K7's dense block update (N = 65 does not), most
+            # tracks must not be 11 - 15-slot ones with none longer, K6-K7 must take all remainder rows as they are
+            n_mid, n_long = sum(WIDE_SPAN < s <= SPLIT_SPAN for s in span), sum(s > SPLIT_SPAN for s in span)
+            direct = 16384 if 6 * N > 186 else 3840
+            keep = n_long == 0 and (2 * n_mid > F or 6 * n_mid > (direct if 6 * N > 186 else min(direct, REM_DIRECT_MID)))
+            total = sum(o.rem_cap for o, _ in shard_orders(1))
+            want = 10 < N <= 37 and n_mid + n_long > 0 and not keep and total <= direct
+            assert rule["split"] == want, (N, text_of(b))
+            orders = shard_orders(int(want))
+            band = [o.entries[:n - o.Fw] + o.entries[n:n + o.nNarrow] for o, n in orders]      # short tracks and narrow blocks
+            assert rule["span"] == max(e["hi"] - e["lo"] + 1 for es in band for e in es)
+            assert rule["rows"] == -(-max(o.rem_cap for o, _ in orders) // 16) * 16 and rule["total"] == sum(o.rem_cap for o, _ in orders)
+            flags = np.zeros((S, N), dtype=np.uint8)
+            for r, es in enumerate(band):
+                flags[r, [e["lo"] for e in es]] = 1
+            assert np.array_equal(rule["flags"], flags)
+            n_split += want
+            n_whole += not want
+    assert n_split > 20 and n_whole > 20
+
+
+def text_of(b):
+    return " ".join(map(str, b["view_ptr"])) + " | " + " ".join(map(str, b["obs_slot"]))

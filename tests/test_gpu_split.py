@@ -263,3 +263,70 @@ def test_stress_ragged_long_tracks_against_oracle():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "tools", "stress_split.py"), "40", "24"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "960 calls, 0 bad" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+
+
+def _kept_views(prob, keep, order=None):
+    """Track j of `prob` with the views keep[j] only (positions in the track, in the order given), the tracks in `order`."""
+    idx = [prob.view_ptr[j] + np.asarray(k) for j, k in enumerate(keep)]
+    sub = synth.UpdateProblem(**{**prob.__dict__, "view_ptr": np.concatenate([[0], np.cumsum([len(k) for k in keep])]).astype(np.int32),
+                                 "obs_uv": prob.obs_uv[np.concatenate(idx)], "obs_slot": prob.obs_slot[np.concatenate(idx)]})
+    return sub if order is None else sub.take(order)
+
+
+def _model_order(prob):
+    """batch_order_model.py on the batch: what csrc/batch_order.h makes of it in an engine of its own (test_batch_order.py)."""
+    from batch_order_model import Order, batch, batch_lines
+    o = Order()
+    lines = batch_lines(batch(prob.N, prob.view_ptr, prob.obs_slot, maxM=20, split=1), o)
+    assert lines[3] == "build 0"
+    return o
+
+
+def test_the_device_sees_the_order_the_host_model_states():
+    """Every class of track in one small shuffled batch (N = 20: every track of the base problem has a view in every slot, the
+    kept views make the class): short tracks, ordered tracks over 11 - 15 slots, ordered tracks over 16 - 20 slots with a
+    one-view group (no narrow block) -- a stretch WITHOUT a view needs three stretches, i.e. more than 20 slots: the CPU test
+    has those --, long tracks with their views reversed (not split).  debug_split and the blocks' parent tracks as the device
+    arrays name them (`perm`, `h_parent`, the block order) equal the model's; a second batch, most of it 11 - 15-slot tracks
+    and none longer, keeps the 90-column tiles."""
+    from msckf_amd.api import UpdateEngine
+    base = synth.make_problem(20, 48, 20, seed=7)
+    assert np.all(np.diff(base.view_ptr) == 20)
+    rng = np.random.default_rng(7)
+    keep = []
+    for j in range(16):                      # short: 2 - 6 views within 10 slots
+        s0 = int(rng.integers(0, 11))
+        keep.append(s0 + np.sort(rng.choice(10, size=2 + j % 5, replace=False)))
+    for j in range(8):                       # 11 - 15 slots, ordered
+        span = 11 + j % 5
+        s0 = int(rng.integers(0, 21 - span))
+        keep.append(s0 + np.concatenate([[0], 1 + np.sort(rng.choice(span - 2, size=3 + j % 4, replace=False)), [span - 1]]))
+    for j in range(12):                      # 16 - 20 slots, ordered: views in the first stretch and the last slot alone
+        span = 16 + j % 5
+        s0 = j % (21 - span)
+        keep.append(np.array([0, 1, 2, 9, 17, 18]) if j == 0 else s0 + np.array([0, 1, 2, 4 + j % 3, span - 1]))
+    for j in range(6):                       # more than 15 slots, views reversed: long, not split
+        span = 16 + j % 5
+        keep.append((j % (21 - span) + np.arange(span))[::-1])
+    prob = _kept_views(base.take(np.arange(len(keep))), keep, rng.permutation(len(keep)))       # (the classes make 42 tracks of the 48)
+    want = _model_order(prob)
+    # (the 11 - 15-slot tracks are split too: 20 split tracks of two stretches each, both with a view)
+    assert prob.F == 42 and want.Fw == 20 and want.rem_cap == 3 * 2 * 20
+    assert sum(sp.count("-1") for sp in want.lines if sp.startswith("split")) >= 20 * 4 + 11     # (one-view groups: no narrow block)
+    with UpdateEngine(max_clones=20, max_features=64, max_track=20) as e:
+        _check(e, prob)
+        s = e.debug_split()
+        assert (s["long_tracks"], s["narrow_blocks"], s["remainder_rows_cap"], s["entries"]) == (want.Fw, want.nNarrow, want.rem_cap, want.Fs)
+        parents = [want.perm[k["parent"]] for k in want.entries[prob.F:]]
+        assert np.array_equal(e.gate_codes()[2], parents)
+        # most tracks over 11 - 15 slots, none longer
+        keep = [keep[j] for j in range(12)]
+        for j in range(18):
+            span = 11 + j % 5
+            s0 = int(rng.integers(0, 21 - span))
+            keep.append(s0 + np.concatenate([[0], 1 + np.sort(rng.choice(span - 2, size=2 + j % 5, replace=False)), [span - 1]]))
+        p2 = _kept_views(synth.make_problem(20, 30, 20, seed=8), keep, rng.permutation(30))
+        w2 = _model_order(p2)
+        assert w2.Fw == 0 and w2.Fs == 30
+        _check(e, p2)
+        assert e.debug_split()["long_tracks"] == 0 and e.debug_split()["entries"] == 30

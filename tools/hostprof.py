@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Host-side phases of the drop-in call (MSCKF_HOSTPROF=1 prints them when the engine closes): rotating batches at (N, F, M)."""
+"""Host-side phases of the drop-in call (MSCKF_HOSTPROF=1 prints them when the engine closes): rotating batches at (N, F, M);
+a fourth argument `ragged`: tracks of 2 .. M views (long ones are split)."""
 import os, sys, time
 os.environ["MSCKF_HOSTPROF"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -7,7 +8,8 @@ import numpy as np, msckf_amd
 from msckf_amd import synth
 from msckf_amd.api import UpdateEngine
 N, F, M = (int(x) for x in (sys.argv[1:4] + ["30", "2000", "10"][len(sys.argv) - 1:]))
-probs = [synth.make_problem(N, F, M, seed=sd) for sd in range(4)]
+kw = {"variable_tracks": True, "min_track": 2} if "ragged" in sys.argv[4:] else {}
+probs = [synth.make_problem(N, F, M, seed=sd, **kw) for sd in range(4)]
 with UpdateEngine(max_clones=N, max_features=F, max_track=M) as eng:
     for i in range(40): eng.update_problem(probs[i % 4])
     best = 1e9

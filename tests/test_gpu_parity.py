@@ -6,6 +6,7 @@ Tolerance: 1e-8 relative on dx and P+ (BASELINE.json north_star); observed ~1e-1
 import numpy as np
 import pytest
 
+import filter_prior as fp
 from conftest import golden_cases, load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +34,12 @@ def test_golden(eng, case):
     assert rel_err(res.dx, ref["dx"]) < TOL
     assert rel_err(res.P_new, ref["P_new"]) < TOL
     assert np.array_equal(res.P_new, res.P_new.T)
+    if case.endswith("_B") or case == "edge_gauge_prior":
+        # priors whose sigmas span orders of magnitude: every entry in units of its own sigmas, and the update term by itself
+        # (tests/filter_prior.py: what the Frobenius norm over the whole array cannot see there)
+        s_dx, s_P, u_P = fp.metrics(res.dx, res.P_new, ref, prob.P)[2:]
+        print(f"FILTERPRIOR golden_{case} scaled dx {s_dx:.2e} scaled P {s_P:.2e} update term {u_P:.2e}")
+        assert s_dx < TOL and s_P < TOL and u_P < TOL, (s_dx, s_P, u_P)
     if res.status == 0:
         # basis-invariant check of the compressed system: T^T T = H^T H, T^T r_n = H^T r
         T, rn = eng.debug_compressed()

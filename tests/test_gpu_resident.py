@@ -6,6 +6,7 @@ for single steps at full window size.  Tolerance 1e-8 relative (BASELINE.json); 
 import numpy as np
 import pytest
 
+import filter_prior as fp
 from conftest import load_sequence, rel_err, sequence_cases
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,7 @@ def test_resident_run_tracks_the_reference(eng, case):
     from msckf_amd import propagation, synth
     head, ops = load_sequence(case)
     eng.set_prior(head["P0"], head["gravity"], head["K"], float(head["sigma"]))
-    worst = 0.0
+    worst = worst_scaled = 0.0
     for op in ops:
         if op["kind"] == 0:
             Phi, Q = propagation.imu_transition(op["R"], op["t"], op["v"], op["R0"], op["t0"], op["v0"], op["gyro"],
@@ -61,6 +62,10 @@ def test_resident_run_tracks_the_reference(eng, case):
         worst = max(worst, err)
         assert err < TOL, (op["kind"], err)
         assert np.array_equal(P, P.T)
+        scaled = fp.scaled_P(P, op["P_after"])                # every entry in units of its own sigmas (tests/filter_prior.py)
+        worst_scaled = max(worst_scaled, scaled)
+        assert scaled < TOL, (op["kind"], scaled)
+    print(f"FILTERPRIOR resident_{case} rel_err {worst:.2e} scaled P {worst_scaled:.2e}")
     assert worst < 1e-10
 
 

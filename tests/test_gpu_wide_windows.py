@@ -26,24 +26,26 @@ TOL32_DX, TOL32_P = 1e-4, 1e-5           # dtype = f32 (tests/test_gpu_f32.py, D
 MAX_N = 221                              # 15 (15 + 6 N) + 225 doubles of k_propagate's LDS tile <= 159 KiB
 
 
-def short_problem(N, seed, F=90):
-    """test_every_window_size's batch: short ragged tracks (at most 10 views), outliers on both sides of the gate."""
+def short_problem(N, seed, F=90, **state):
+    """test_every_window_size's batch: short ragged tracks (at most 10 views), outliers on both sides of the gate.
+    `state`: P= and poses= of synth.make_problem, for a prior other than recipe A (tests/filter_prior.py)."""
     from msckf_amd import synth
     M = max(1, min(N, 2 + N % 9))
-    return synth.make_problem(N, F, M, seed=seed, variable_tracks=M > 2, outlier_fraction=0.15, outlier_px=300.0)
+    return synth.make_problem(N, F, M, seed=seed, variable_tracks=M > 2, outlier_fraction=0.15, outlier_px=300.0, **state)
 
 
-def long_problem(N, seed, F=90, M=31, min_track=2):
+def long_problem(N, seed, F=90, M=31, min_track=2, **state):
     from msckf_amd import synth
     return synth.make_problem(N, F, M, seed=seed, variable_tracks=True, min_track=min_track, outlier_fraction=0.15,
-                              outlier_px=300.0)
+                              outlier_px=300.0, **state)
 
 
-def full_problem(N, seed):
+def full_problem(N, seed, **state):
     """Short ragged tracks (2 - 10 views) and enough of them (F = 2 N) that the stack has more rows than the window has columns:
     T is full, so every column of K and of the solve is exercised."""
     from msckf_amd import synth
-    return synth.make_problem(N, max(90, 2 * N), 10, seed=seed, variable_tracks=True, outlier_fraction=0.15, outlier_px=300.0)
+    return synth.make_problem(N, max(90, 2 * N), 10, seed=seed, variable_tracks=True, outlier_fraction=0.15, outlier_px=300.0,
+                              **state)
 
 
 def problem(kind, N, seed):

@@ -161,6 +161,38 @@ int msckf_update(msckf_ctx* ctx, int32_t N, const double* P,
                  const double* chi2_crit, int32_t n_crit,
                  double* dx, double* P_out, uint8_t* accepted, msckf_stats* stats);
 
+/* ---- per-view measurement noise ---------------------------------------- *
+ * The reference weights every view alike: R_o = sigma^2 I (MSCKF.py:589), and sigma^2 I in the gate (:562).
+ * With sigma_view[sumM] (input order of the views, the order of obs_uv; every entry finite and > 0, same
+ * units as sigma) the update is the reference's with R_o = blockdiag(sigma_v^2 I_2), and the two rows of
+ * view v carry sigma_v^2 in the gate.  It is computed in whitened form: with w_v = sigma / sigma_v (the
+ * fp64 quotient, exactly 1 where sigma_v == sigma) the view's residual r_i, its OC-projected H_xi
+ * (:532-540) and its H_fi (:536) are multiplied by w_v BEFORE the null-space projection (:550).  The left
+ * null space is then that of diag(w) H_f, the projected noise is sigma^2 I again, and gamma, K, dx and P+
+ * are those of the R_o form; everything behind K1 is the unweighted code.  sigma_view == sigma everywhere
+ * gives bit for bit the result without weights; sigma_view == sigma / c everywhere that of sigma / c.
+ *
+ * msckf_update_sigma is msckf_update with the array (nullable) behind idp_rho; msckf_update calls it with
+ * NULL.  The weights ride in the pinned upload image beside obs_uv, the host workers validate them with the
+ * other arrays, and the device brings them into the pipeline's order with the tracks. */
+int msckf_update_sigma(msckf_ctx* ctx, int32_t N, const double* P,
+                       const double* cam_R, const double* cam_t,
+                       const double* cam_R0, const double* cam_t0,
+                       const double* gravity, const double* Kinv, double sigma,
+                       int32_t F, const int32_t* view_ptr, const double* obs_uv,
+                       const int32_t* obs_slot, const double* idp_base,
+                       const double* idp_m, const double* idp_rho, const double* sigma_view,
+                       const double* chi2_crit, int32_t n_crit,
+                       double* dx, double* P_out, uint8_t* accepted, msckf_stats* stats);
+/* Resident path: the weights of the loaded batch, after msckf_set_features, msckf_tracks_load or
+ * msckf_tracks_load_where (where msckf_set_tracks stands in the call order; like it, it returns with the
+ * upload done).  NULL clears them.  They belong to the batch: the next batch load clears them, and so does
+ * msckf_set_state (w_v was taken at the sigma it replaces).  msckf_run, msckf_run_compress,
+ * msckf_run_timed, msckf_run_select + msckf_run and msckf_replan honour them; msckf_debug_gate reports the
+ * weighted gamma.  Errors, with nothing changed: MSCKF_ERR_STATE without a loaded batch, MSCKF_ERR_ARG for
+ * an entry that is not finite or not > 0. */
+int msckf_set_view_sigma(msckf_ctx* ctx, const double* sigma_view);
+
 /* ---- resident path: the same update split so inputs can stay in HBM ---- */
 /* Upload filter state read by update(): P, clone poses, gravity, K^-1, sigma, chi2 table. */
 int msckf_set_state(msckf_ctx* ctx, int32_t N, const double* P,

@@ -40,6 +40,7 @@ SYMBOLS = [
     "msckf_tracks_count", "msckf_tracks_dropped",
     "msckf_tracks_frame", "msckf_tracks_load_where", "msckf_tracks_counters", "msckf_tracks_clone_views",
     "msckf_tracks_match", "msckf_tracks_match_frame", "msckf_tracks_descriptor",
+    "msckf_update_sigma", "msckf_set_view_sigma",
 ]
 
 
@@ -129,6 +130,12 @@ def load():
     lib.msckf_update.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_int32, _ip, _dp,
                                  _ip, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _up, C.POINTER(Stats)]
     lib.msckf_update.restype = C.c_int
+    # msckf_update with sigma_view[sumM] (nullable) behind idp_rho
+    lib.msckf_update_sigma.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_int32, _ip, _dp,
+                                       _ip, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _up, C.POINTER(Stats)]
+    lib.msckf_update_sigma.restype = C.c_int
+    lib.msckf_set_view_sigma.argtypes = [vp, _dp]
+    lib.msckf_set_view_sigma.restype = C.c_int
     lib.msckf_set_state.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, C.c_int32]
     lib.msckf_set_state.restype = C.c_int
     lib.msckf_set_features.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp]

@@ -111,6 +111,7 @@ class UpdateEngine:
         self.max_clones, self.max_features, self.max_track = max_clones, max_features, max_track
         self._N = 0
         self._F = 0
+        self._views = None      # views of the loaded batch where the caller's arrays told (set_view_sigma checks its length)
         self._desc_dim = 0      # D of the last tracks_match_frame that went in (track_descriptor trims to it)
 
     # -- lifetime -----------------------------------------------------------
@@ -150,14 +151,16 @@ class UpdateEngine:
         P_out = np.empty((d, d))
         acc = np.zeros(max(F, 1), dtype=np.uint8)
         st = _ffi.Stats()
-        rc = self._lib.msckf_update(
+        # (per-view noise: sigma_view behind idp_rho, or NULL -- msckf_update is this call with NULL)
+        vs = None if prob.view_sigma is None else self._view_sigma(prob.view_sigma, int(a["view_ptr"][-1]))
+        rc = self._lib.msckf_update_sigma(
             self._h, N, _ffi.dptr(a["P"]), _ffi.dptr(a["cam_R"]), _ffi.dptr(a["cam_t"]), _ffi.dptr(a["cam_R0"]),
             _ffi.dptr(a["cam_t0"]), _ffi.dptr(a["g"]), _ffi.dptr(a["Kinv"]), float(prob.sigma), F,
             _ffi.iptr(a["view_ptr"]), _ffi.dptr(a["obs_uv"]), _ffi.iptr(a["obs_slot"]), _ffi.dptr(a["idp_base"]),
-            _ffi.dptr(a["idp_m"]), _ffi.dptr(a["idp_rho"]), _ffi.dptr(chi), int(chi.size),
+            _ffi.dptr(a["idp_m"]), _ffi.dptr(a["idp_rho"]), None if vs is None else _ffi.dptr(vs), _ffi.dptr(chi), int(chi.size),
             _ffi.dptr(dx), _ffi.dptr(P_out), _ffi.uptr(acc), C.byref(st))
         self._check(rc)
-        self._N, self._F = N, F
+        self._N, self._F, self._views = N, F, None if vs is None else int(vs.size)
         return UpdateResult(rc, dx, P_out, acc[:F].copy(), st.as_dict())
 
     _kinv_cache = (None, None)
@@ -199,10 +202,34 @@ class UpdateEngine:
             self._h, prob.F, _ffi.iptr(a["view_ptr"]), _ffi.dptr(a["obs_uv"]), _ffi.iptr(a["obs_slot"]),
             _ffi.dptr(a["idp_base"]), _ffi.dptr(a["idp_m"]), _ffi.dptr(a["idp_rho"])), allow_noop=False)
         self._F = prob.F
+        self._views = int(a["view_ptr"][-1])
 
     def load(self, prob: UpdateProblem):
         self.set_state(prob)
         self.set_features(prob)
+        if prob.view_sigma is not None:
+            self.set_view_sigma(prob.view_sigma)
+
+    @staticmethod
+    def _view_sigma(view_sigma, n_views: int) -> np.ndarray:
+        vs = _ffi.f64(np.asarray(view_sigma, dtype=np.float64).reshape(-1))
+        if vs.size != n_views:
+            raise ValueError(f"view_sigma holds {vs.size} entries, the batch {n_views} views")
+        return vs
+
+    def set_view_sigma(self, view_sigma=None):
+        """Per-view measurement noise of the loaded batch (`msckf_set_view_sigma`): one standard deviation per view, in
+        the input order of the views and in `sigma`'s units; `None` clears.  The next batch load or `set_state` clears
+        them too.  Raises `ValueError` for a wrong length, `EngineError` (`ERR_ARG`) for an entry that is not finite or
+        not > 0 and (`ERR_STATE`) without a loaded batch -- the weights in force stay as they were."""
+        if view_sigma is None:
+            self._check(self._lib.msckf_set_view_sigma(self._h, None), allow_noop=False)
+            return
+        vs = _ffi.f64(np.asarray(view_sigma, dtype=np.float64).reshape(-1))
+        n = getattr(self, "_views", None)      # (views of the loaded batch; a batch of the track store: the caller counts them)
+        if n is not None and vs.size != n:
+            raise ValueError(f"view_sigma holds {vs.size} entries, the loaded batch {n} views")
+        self._check(self._lib.msckf_set_view_sigma(self._h, _ffi.dptr(vs)), allow_noop=False)
 
     def run(self):
         self._check(self._lib.msckf_run(self._h), allow_noop=False)
@@ -446,6 +473,7 @@ class UpdateEngine:
         self._check(self._lib.msckf_tracks_load(self._h, int(i.size), _ffi.iptr(i), _ffi.iptr(lo), _ffi.iptr(tr)),
                     allow_noop=False)
         self._F = int(i.size)
+        self._views = None
 
     def tracks_frame(self, ids, uv, score, K, epipolar_threshold: float = 5.0, homography_threshold: float = 5.0):
         """A frame's matches on the store (reference `MSCKF.py:332-438`): each (track id, keypoint, score) is tested against
@@ -541,6 +569,7 @@ class UpdateEngine:
         self._check(self._lib.msckf_tracks_load_where(self._h, int(sl.size), _ffi.iptr(sl), C.addressof(F), _ffi.iptr(ids), cap),
                     allow_noop=False)
         self._F = int(F.value)
+        self._views = None
         return ids[:self._F].copy()
 
     def tracks_counters(self, ids):
@@ -852,7 +881,7 @@ class UpdateEngine:
         return T, rn
 
     # -- reference-shaped drop-in ---------------------------------------------
-    def update(self, filt, features) -> int:
+    def update(self, filt, features, view_sigma=None) -> int:
         """Drop-in for `MSCKF.update(features)` (reference `MSCKF.py:570-609`)
         including `correct` (`:611-661`).  `filt` is any object with the
         attributes the reference method reads: `state.cameras` (ordered mapping
@@ -860,10 +889,15 @@ class UpdateEngine:
         `state.covariance`, `state.imu` (`W_gravity`, `T_W_Ii`, `v_W_Ii`,
         `gyroscope_bias`, `accelerometer_bias`), `K`, `sigma_image`,
         `number_of_residuals_discarded_for_gasting_test`.
+        `view_sigma`: optional mapping feature key -> one standard deviation per view, in the order of
+        `Feature.keypoints` and in `sigma_image`'s units (R_o = blockdiag(sigma_v^2 I_2) in place of `:589`; a
+        feature the mapping does not name stays at `sigma_image`).  `None`: the reference's update.
         Returns the status (0 updated / 1 no-op); mutates `filt` like the reference."""
-        from .pack import problem_from_reference
+        from .pack import problem_from_reference, view_sigma_from_reference
         from .inject import inject_state
         prob = problem_from_reference(filt, features)
+        if view_sigma is not None:
+            prob.view_sigma = view_sigma_from_reference(features, view_sigma, prob.sigma)
         res = self.update_problem(prob)
         filt.number_of_residuals_discarded_for_gasting_test += res.n_rejected        # MSCKF.py:578
         if res.status != 0:
@@ -872,18 +906,21 @@ class UpdateEngine:
         inject_state(filt.state, res.dx)                                              # MSCKF.py:616-661
         return 0
 
-    def process_features(self, filt) -> int:
+    def process_features(self, filt, view_sigma=None) -> int:
         """Drop-in for `MSCKF.process_features()` (reference `MSCKF.py:450-456`):
         `get_valid_features(self.features)` and `update(valid_features)` in one device pass,
         then `remove_features(lost_features)` through the filter's own method.  Mutates the
         features' inverse-depth points (`:488`) and the filter like the reference does.
+        `view_sigma`: as in `update`, keyed like `filt.features`.
         Returns 0 updated / 1 no-op."""
-        from .pack import problem_from_reference, select_params_from_reference, tracks_from_reference
+        from .pack import problem_from_reference, select_params_from_reference, tracks_from_reference, view_sigma_from_reference
         from .inject import inject_state
         feats = filt.features
         if len(feats) == 0:
             return 1
         prob = problem_from_reference(filt, feats)
+        if view_sigma is not None:
+            prob.view_sigma = view_sigma_from_reference(feats, view_sigma, prob.sigma)
         self.load(prob)
         self.set_tracks(tracks_from_reference(feats))
         self.run_select(select_params_from_reference(filt), prob.K)

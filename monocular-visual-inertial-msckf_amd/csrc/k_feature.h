@@ -46,6 +46,8 @@ struct FeatureArgs {
     const int* view_ptr;         // [F+1] CSR, in SORTED feature order
     const double* obs_uv;        // [sumM*2]
     const int* obs_slot;         // [sumM]
+    const double* obs_w;         // optional [sumM], sorted view order: w_v = sigma / sigma_v of a view with a noise level of its own
+                                 //   (both rows of view v of [r | H_x | H_f] are scaled by it in K1; null: every view at sigma)
     const double* idp_base;      // [F*3]
     const double* idp_m;         // [F*3]
     const double* idp_rho;       // [F]
@@ -294,6 +296,8 @@ __global__ __launch_bounds__(64 * NWV, NWV > 1 ? 1 : (RMAX <= 24 ? 3 : 2)) void 
         const double Wy = R[3] * px + R[4] * py + R[5] * pz + t[1];
         const double Wz = R[6] * px + R[7] * py + R[8] * pz + t[2];
         const double u = p.obs_uv[2 * o], v = p.obs_uv[2 * o + 1];
+        double wv = 1.0;
+        if (p.obs_w) wv = p.obs_w[o];           // (uniform; asked for here, used at the end of K1)
         const double zx = p.Kinv[0] * u + p.Kinv[1] * v + p.Kinv[2];
         const double zy = p.Kinv[3] * u + p.Kinv[4] * v + p.Kinv[5];
         const double zw = p.Kinv[6] * u + p.Kinv[7] * v + p.Kinv[8];
@@ -333,6 +337,14 @@ __global__ __launch_bounds__(64 * NWV, NWV > 1 ? 1 : (RMAX <= 24 ? 3 : 2)) void 
             const double aud = au * (1.0 / den);
             a0 -= aud * u0; a1 -= aud * u1; a2 -= aud * u2;
             a3 -= aud * u3; a4 -= aud * u4; a5 -= aud * u5;
+        }
+        // per-view noise: R_o = blockdiag(sigma_v^2 I_2) in whitened form -- the view's rows of r, H_x and H_f times
+        // w_v = sigma / sigma_v, ONCE and in front of everything that forms Z, V or the gate's E: the null space below is that of
+        // diag(w) H_f, so the projected noise is sigma^2 I again and nothing behind K1 knows of the weights
+        if (p.obs_w) {
+            res *= wv;
+            a0 *= wv; a1 *= wv; a2 *= wv; a3 *= wv; a4 *= wv; a5 *= wv;
+            h0 *= wv; h1 *= wv; h2 *= wv;
         }
     }
 

@@ -91,4 +91,17 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather(GatherArgs p) {
     }
 }
 
+// The per-view weights of a batch (msckf_set_view_sigma, msckf_update_sigma) by the same records: entry s of the sorted arrays
+// takes the views [a, a + M) of the caller's order to [o, o + M).  A launch of its own, only for batches that carry weights:
+// k_gather stays what it is for those that do not.
+__global__ __launch_bounds__(GATHER_THREADS) void k_gather_w(const GatherRec* __restrict__ rec, const double* __restrict__ w_in,
+                                                             double* __restrict__ w, int F, int sumM_in, int sumM) {
+    const int t = threadIdx.x, v = t & 31;
+    const int s = blockIdx.x * (GATHER_THREADS / 32) + (t >> 5);
+    if (s >= F) return;
+    const GatherRec r = rec[s];
+    for (int i = v; i < r.M; i += 32)
+        if (r.a + i < sumM_in && r.o + i < sumM) w[r.o + i] = w_in[r.a + i];
+}
+
 }  // namespace msckf

@@ -396,6 +396,13 @@ struct msckf_ctx {
     std::vector<int> x_bounds;            // [n_shards + 1] shard r holds features [b[r], b[r+1]) of the whole batch; empty = off
     int xmask_doubles = 0;                // doubles of the record head that carry the shard's gate bytes (input order)
     Buf dPerm;                            // sorted position -> input index, on the device (view into the feature arena)
+    // per-view noise (msckf_set_view_sigma, msckf_update_sigma): w_v = sigma / sigma_v.  The weights belong to the batch: they
+    // sit behind its raw image in the caller's view order (pinned and in HBM, w_raw_off) and, permuted by k_gather_w with the
+    // batch's own records, behind its sorted image (dObsW, a view into the feature arena); have_w says K1 reads them
+    bool have_w = false;
+    size_t w_raw_off = 0;
+    Buf dObsW;
+    const GatherRec* gather_rec = nullptr; // the batch's records where k_gather read them (pinned host image or the raw arena)
     std::vector<double> chi2_cache;
     bool defer_state_sync = false;        // msckf_update: the feature upload's sync covers the state upload
     bool oneshot = false;                 // msckf_update: set_features uploads, launches K1-K4 and plans K5 meanwhile, no sync
@@ -1349,6 +1356,7 @@ int launch_feature(msckf_ctx* c) {
     a.F = c->F; a.ldp = c->d;
     a.view_ptr = ptr<int>(c->dViewPtr); a.obs_uv = ptr<double>(c->dObsUV); a.obs_slot = ptr<int>(c->dObsSlot);
     a.idp_base = ptr<double>(c->dBase); a.idp_m = ptr<double>(c->dMvec); a.idp_rho = ptr<double>(c->dRho);
+    a.obs_w = c->have_w ? ptr<double>(c->dObsW) : nullptr;
     a.cam_R = ptr<double>(c->dCamR); a.cam_t = ptr<double>(c->dCamT);
     a.cam_R0 = ptr<double>(c->dCamR0); a.cam_t0 = ptr<double>(c->dCamT0);
     a.P = ptr<double>(c->dP); a.chi2 = ptr<double>(c->dChi2); a.n_chi2 = c->n_chi2;
@@ -2404,7 +2412,20 @@ int msckf_set_state(msckf_ctx* c, int32_t N, const double* P, const double* cam_
     c->us_h2d = (float)(now_us() - t0);
     c->have_state = true;
     c->last.ran = false;
+    c->have_w = false;                    // w_v = sigma / sigma_v was taken at the sigma that is replaced here
     tracks_clear(c);                      // clone slots lose their meaning
+    return MSCKF_OK;
+}
+
+// The weights of the current batch, as they lie behind the pinned image in the caller's view order: up by DMA, then into the
+// sorted order by the batch's own records (k_gather_w), in the stream in front of K1
+static int launch_gather_w(msckf_ctx* c) {
+    const int Fs = c->ord.Fs;
+    char* draw = static_cast<char*>(c->dRawArena.p);
+    HIPCHK(c, hipMemcpyAsync(draw + c->w_raw_off, static_cast<char*>(c->hFeat) + c->w_raw_off, (size_t)c->sumM * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_gather_w, dim3((Fs + GATHER_THREADS / 32 - 1) / (GATHER_THREADS / 32)), dim3(GATHER_THREADS), 0, c->stream,
+                       c->gather_rec, reinterpret_cast<const double*>(draw + c->w_raw_off), ptr<double>(c->dObsW), Fs, c->sumM, c->ord.sumMs);
+    HIPCHK(c, hipGetLastError());
     return MSCKF_OK;
 }
 
@@ -2412,7 +2433,7 @@ int msckf_set_state(msckf_ctx* c, int32_t N, const double* P, const double* cam_
 // (msckf_set_features: staged through the pinned image) or the track store (emit != nullptr: written in HBM by k_track_emit).
 static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const double* obs_uv,
                              const int32_t* obs_slot, const double* idp_base, const double* idp_m,
-                             const double* idp_rho, const TrackEmitSrc* emit) {
+                             const double* idp_rho, const TrackEmitSrc* emit, const double* sigma_view = nullptr) {
     if (!c || F < 0 || F > c->maxF) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     if (F > 0 && (!view_ptr || !obs_slot || (!emit && (!obs_uv || !idp_base || !idp_m || !idp_rho)))) return MSCKF_ERR_ARG;
@@ -2429,6 +2450,8 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     c->use_select = false;
     c->batch_from_store = false;
     c->no_wide = false;
+    c->have_w = false;                    // the weights belonged to the batch that is gone
+    c->gather_rec = nullptr;
     if (F == 0) {
         c->F = 0;
         c->sumM = 0; c->ord.reset(); c->nodes.clear(); c->levels.clear(); c->snodes.clear(); c->sfolds.clear(); c->sweep_levels.clear(); c->n_group_merges = 0;
@@ -2467,18 +2490,21 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     }
     const int sumM = view_ptr[F];
     const RawLayout raw = raw_layout(F, sumM);           // (input order; the sort's records behind the arrays)
-    if (c->hFeatCap < raw.pin_bytes) {
+    // (behind the image, in both memories: room for one weight per view -- msckf_set_view_sigma may bring them later)
+    const size_t w_off = (raw.pin_bytes + 15) & ~(size_t)15, img_bytes = w_off + (size_t)sumM * 8;
+    if (c->hFeatCap < img_bytes) {
         if (c->hFeat) HIPCHK(c, hipHostFree(c->hFeat));
         c->hFeat = nullptr; c->hFeatCap = 0;
-        HIPCHK(c, hipHostMalloc(&c->hFeat, raw.pin_bytes + raw.pin_bytes / 2));
-        c->hFeatCap = raw.pin_bytes + raw.pin_bytes / 2;
+        HIPCHK(c, hipHostMalloc(&c->hFeat, img_bytes + img_bytes / 2));
+        c->hFeatCap = img_bytes + img_bytes / 2;
     }
     // small batches: the small arrays reach HBM through a copy KERNEL reading the pinned image (k_stage) and k_gather reads the
     // sort's records from it (zero-copy) -- no copy command but the observations', none of the ~9 us each one waits behind its
     // predecessor; large ones: DMA, beside the host's sort (measured at 10000 tracks: zero-copy 620 us per call, DMA 578)
     static const int zc_max = [] { const char* e = std::getenv("MSCKF_ZEROCOPY_MAX"); return e ? std::atoi(e) : 4096; }();
     const bool zc = F <= zc_max;
-    if (int rca = ensure(c, c->dRawArena, raw.pin_bytes)) return rca;
+    if (int rca = ensure(c, c->dRawArena, img_bytes)) return rca;
+    c->w_raw_off = w_off;
     char* hb = static_cast<char*>(c->hFeat);
     char* draw = static_cast<char*>(c->dRawArena.p);
     const bool par = c->pool && F >= host_par_min();
@@ -2500,7 +2526,10 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     {
         const int nch = par ? std::min(4 * (c->pool->workers() + 1), (F + 255) / 256) : 1;
         std::vector<ScanPart> part(nch);
+        std::vector<unsigned char> w_bad(nch, 0);
         const int maxM = c->maxM;
+        const double sigma = c->sigma;
+        double* hw = reinterpret_cast<double*>(hb + w_off);
         auto validate = [&](int ch) {
             const int f0 = (int)((long long)F * ch / nch), f1 = (int)((long long)F * (ch + 1) / nch);
             const int a0 = view_ptr[f0], a1 = view_ptr[f1];
@@ -2510,6 +2539,13 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
                 std::memcpy(hb + raw.r_m + (size_t)f0 * 24, idp_m + (size_t)f0 * 3, (size_t)(f1 - f0) * 24);
                 std::memcpy(hb + raw.r_rho + (size_t)f0 * 8, idp_rho + f0, (size_t)(f1 - f0) * 8);
             }
+            if (sigma_view) {             // w_v = sigma / sigma_v, the fp64 quotient: exactly 1 where sigma_v == sigma
+                for (int i = a0; i < a1; ++i) {
+                    const double sv = sigma_view[i];
+                    if (!(std::isfinite(sv) && sv > 0.0)) w_bad[ch] = 1;
+                    hw[i] = sigma / sv;
+                }
+            }
             part[ch] = scan_range(N, maxM, split, view_ptr, obs_slot, f0, f1, key_in.data(), M_in.data());
         };
         if (nch > 1) c->pool->run(nch, validate); else validate(0);
@@ -2517,6 +2553,8 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
             if (part[ch].err != kOrderOk) { (void)hipStreamSynchronize(c->stream); return part[ch].err; }      // (the pinned image is in flight)
             tot.add(part[ch]);
         }
+        for (int ch = 0; ch < nch; ++ch)
+            if (w_bad[ch]) { (void)hipStreamSynchronize(c->stream); return MSCKF_ERR_ARG; }
     }
     const int Mmax = tot.Mmax_all();
     // mostly 11 - 15 slots and none more: the 90-column band pipeline for all of them (keeps_wide_tiles)
@@ -2560,8 +2598,9 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
 
     // sorted image (what the kernels read), written by k_gather: Fs entries, sumMs views
     const SortedLayout so = sorted_layout(Fs, sumMs, sizeof(FeatInfo));
-    if (c->dFeatArena.bytes < so.feat_bytes && c->run_pending) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->run_pending = false; }
-    if (int rca = ensure(c, c->dFeatArena, so.feat_bytes)) return rca;
+    const size_t so_w_off = (so.feat_bytes + 15) & ~(size_t)15, so_bytes = so_w_off + (size_t)sumMs * 8;   // + the weights, sorted
+    if (c->dFeatArena.bytes < so_bytes && c->run_pending) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->run_pending = false; }
+    if (int rca = ensure(c, c->dFeatArena, so_bytes)) return rca;
     set_view(c->dObsUV, c->dFeatArena.p, so.o_uv, (size_t)sumMs * 16);
     set_view(c->dBase, c->dFeatArena.p, so.o_base, (size_t)Fs * 24);
     set_view(c->dMvec, c->dFeatArena.p, so.o_m, (size_t)Fs * 24);
@@ -2572,6 +2611,7 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     set_view(c->dFmin, c->dFeatArena.p, so.o_fmin, (size_t)Fs * 4);
     set_view(c->dFeatInfo, c->dFeatArena.p, so.o_info, (size_t)Fs * sizeof(FeatInfo));
     set_view(c->dPerm, c->dFeatArena.p, so.o_perm, (size_t)Fs * 4);
+    set_view(c->dObsW, c->dFeatArena.p, so_w_off, (size_t)sumMs * 8);
     // gate results: rank[Fs] (int) then accepted[Fs] (byte), contiguous so they come back in one copy
     if ((size_t)5 * Fs > c->dGateArena.bytes || (size_t)5 * Fs > c->hGateCap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2608,6 +2648,11 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
         g.F = Fs; g.sumM = sumMs;
         hipLaunchKernelGGL(k_gather, dim3((Fs + GATHER_THREADS / 32 - 1) / (GATHER_THREADS / 32)), dim3(GATHER_THREADS), 0, c->stream, g);
         HIPCHK(c, hipGetLastError());
+        c->gather_rec = g.rec;
+    }
+    if (sigma_view) {
+        if (int rcw = launch_gather_w(c)) return rcw;
+        c->have_w = true;
     }
     // (k_lsweep's zero words behind the stack are written by k_feature itself: one launch less in front of it)
     c->feature_launched = false;
@@ -2666,6 +2711,27 @@ int msckf_set_features(msckf_ctx* c, int32_t F, const int32_t* view_ptr, const d
                        const int32_t* obs_slot, const double* idp_base, const double* idp_m,
                        const double* idp_rho) {
     return set_features_impl(c, F, view_ptr, obs_uv, obs_slot, idp_base, idp_m, idp_rho, nullptr);
+}
+
+int msckf_set_view_sigma(msckf_ctx* c, const double* sigma_view) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->have_state || !c->have_features) return MSCKF_ERR_STATE;
+    if (!sigma_view || c->F == 0) { c->have_w = false; return MSCKF_OK; }
+    const int sumM = c->sumM;
+    for (int i = 0; i < sumM; ++i)
+        if (!(std::isfinite(sigma_view[i]) && sigma_view[i] > 0.0)) return MSCKF_ERR_ARG;      // (nothing changed)
+    if (!c->gather_rec || !c->ord.valid) return MSCKF_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the image's weights may still be on their way up, and a run nobody waited for may be reading the sorted ones
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream2));
+    double* hw = reinterpret_cast<double*>(static_cast<char*>(c->hFeat) + c->w_raw_off);
+    const double sigma = c->sigma;
+    for (int i = 0; i < sumM; ++i) hw[i] = sigma / sigma_view[i];
+    if (int rcw = launch_gather_w(c)) return rcw;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->have_w = true;
+    return MSCKF_OK;
 }
 
 int msckf_run(msckf_ctx* c) {
@@ -2874,6 +2940,15 @@ int msckf_update(msckf_ctx* c, int32_t N, const double* P, const double* cam_R, 
                  double sigma, int32_t F, const int32_t* view_ptr, const double* obs_uv, const int32_t* obs_slot,
                  const double* idp_base, const double* idp_m, const double* idp_rho, const double* chi2_crit,
                  int32_t n_crit, double* dx, double* P_out, uint8_t* accepted, msckf_stats* stats) {
+    return msckf_update_sigma(c, N, P, cam_R, cam_t, cam_R0, cam_t0, gravity, Kinv, sigma, F, view_ptr, obs_uv, obs_slot,
+                              idp_base, idp_m, idp_rho, nullptr, chi2_crit, n_crit, dx, P_out, accepted, stats);
+}
+
+int msckf_update_sigma(msckf_ctx* c, int32_t N, const double* P, const double* cam_R, const double* cam_t,
+                       const double* cam_R0, const double* cam_t0, const double* gravity, const double* Kinv,
+                       double sigma, int32_t F, const int32_t* view_ptr, const double* obs_uv, const int32_t* obs_slot,
+                       const double* idp_base, const double* idp_m, const double* idp_rho, const double* sigma_view,
+                       const double* chi2_crit, int32_t n_crit, double* dx, double* P_out, uint8_t* accepted, msckf_stats* stats) {
     if (!c) return MSCKF_ERR_ARG;
     const double tu0 = now_us();
     if (c->main_busy || (c->last.ran && c->fetched_serial != c->last.serial)) {       // work nobody waited for: the side stream below must not overtake it
@@ -2888,7 +2963,7 @@ int msckf_update(msckf_ctx* c, int32_t N, const double* P, const double* cam_R, 
     if (rc != MSCKF_OK) { (void)hipStreamSynchronize(c->stream_up); c->state_pending = false; return rc; }
     c->hp[0] += now_us() - tu0;
     c->oneshot = F > 0;
-    rc = msckf_set_features(c, F, view_ptr, obs_uv, obs_slot, idp_base, idp_m, idp_rho);
+    rc = set_features_impl(c, F, view_ptr, obs_uv, obs_slot, idp_base, idp_m, idp_rho, nullptr, sigma_view);
     c->oneshot = false;
     if (rc != MSCKF_OK) {            // uploads / K1-K4 may be in flight
         (void)hipStreamSynchronize(c->stream_up); (void)hipStreamSynchronize(c->stream);

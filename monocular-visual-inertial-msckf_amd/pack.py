@@ -48,6 +48,22 @@ def problem_from_reference(filt, features) -> UpdateProblem:
         idp_rho=np.asarray(rho, dtype=np.float64), meta={"keys": keys})
 
 
+def view_sigma_from_reference(features, view_sigma, sigma: float) -> np.ndarray:
+    """Per-view standard deviations in the order `problem_from_reference` lays the views down: `view_sigma` maps a
+    feature key to one value per entry of `Feature.keypoints`; a feature it does not name stays at `sigma`."""
+    out = []
+    for key, ft in features.items():                   # dict order, MSCKF.py:573
+        M = len(ft.keypoints)
+        if key in view_sigma:
+            sv = np.asarray(view_sigma[key], dtype=np.float64).reshape(-1)
+            if sv.size != M:
+                raise ValueError(f"view_sigma[{key!r}] holds {sv.size} entries, the feature {M} views")
+        else:
+            sv = np.full(M, float(sigma))
+        out.append(sv)
+    return np.concatenate(out) if out else np.zeros(0)
+
+
 def tracks_from_reference(features) -> TrackTable:
     """What `MSCKF.get_valid_features` reads besides the views (reference
     `MSCKF.py:461-480`): `Feature.lines[i].{base,direction,confidence}` and the frame

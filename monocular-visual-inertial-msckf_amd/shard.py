@@ -7,6 +7,10 @@ K1-K5 on its shard; the only exchange is ONE gather of the compressed blocks
 QR-merges them and runs the serial K6-K7; dx and P+ are then broadcast so every
 rank holds the state for the next update.
 
+Per-view noise (`UpdateProblem.view_sigma`) is sliced with the tracks: `prob.subset(lo, hi)` hands a rank the
+sigmas of its own views and `engine.load` sets them (`msckf_set_view_sigma`).  The blocks and records carry
+whitened rows; the exchange and the merge do not change.
+
 Two drivers:
  * `RcclShardedUpdate` -- the product path: the gather / broadcast run on librccl BEHIND the C-ABI
    (`msckf_comm_*`, enqueued on the engine's stream between its kernels; no PyTorch, no host round trip

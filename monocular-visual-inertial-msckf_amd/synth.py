@@ -46,6 +46,9 @@ class UpdateProblem:
     idp_m: np.ndarray        # (F, 3) InverseDepthPoint.m
     idp_rho: np.ndarray      # (F,)   InverseDepthPoint.rho
     meta: dict = field(default_factory=dict)
+    # optional (sum M,) standard deviation of each view, in sigma's units: R_o = blockdiag(sigma_v^2 I_2) in place of the
+    # reference's sigma^2 I (MSCKF.py:589, :562).  None: every view at sigma
+    view_sigma: Optional[np.ndarray] = None
 
     @property
     def N(self) -> int:
@@ -73,7 +76,8 @@ class UpdateProblem:
             gravity=self.gravity, K=self.K, sigma=self.sigma, view_ptr=vp,
             obs_uv=self.obs_uv[rows].reshape(-1, 2), obs_slot=self.obs_slot[rows].astype(np.int32),
             idp_base=self.idp_base[idx].reshape(-1, 3), idp_m=self.idp_m[idx].reshape(-1, 3),
-            idp_rho=self.idp_rho[idx], meta=dict(self.meta, take=idx))
+            idp_rho=self.idp_rho[idx], meta=dict(self.meta, take=idx),
+            view_sigma=None if self.view_sigma is None else np.asarray(self.view_sigma, dtype=np.float64).reshape(-1)[rows])
 
     def subset(self, lo: int, hi: int) -> "UpdateProblem":
         """Contiguous feature shard [lo, hi) with the shared state (P, poses) kept."""
@@ -84,7 +88,8 @@ class UpdateProblem:
             view_ptr=(self.view_ptr[lo:hi + 1] - a).astype(np.int32),
             obs_uv=self.obs_uv[a:b], obs_slot=self.obs_slot[a:b],
             idp_base=self.idp_base[lo:hi], idp_m=self.idp_m[lo:hi], idp_rho=self.idp_rho[lo:hi],
-            meta=dict(self.meta, shard=(lo, hi)))
+            meta=dict(self.meta, shard=(lo, hi)),
+            view_sigma=None if self.view_sigma is None else np.asarray(self.view_sigma, dtype=np.float64).reshape(-1)[a:b])
 
 
 @dataclass
@@ -261,7 +266,11 @@ def concat_problems(a: UpdateProblem, b: UpdateProblem) -> UpdateProblem:
     """The tracks of `b` appended to those of `a` (same state: build `b` with P=a.P, poses=(a.cam_R, a.cam_t))."""
     vp = np.concatenate([a.view_ptr, a.view_ptr[-1] + b.view_ptr[1:]]).astype(np.int32)
     cat = lambda x, y: np.concatenate([x, y])
-    return UpdateProblem(**{**a.__dict__, "view_ptr": vp, "obs_uv": cat(a.obs_uv, b.obs_uv), "obs_slot": cat(a.obs_slot, b.obs_slot),
+    vs = None
+    if a.view_sigma is not None or b.view_sigma is not None:       # (a side without weights: its views at its sigma)
+        side = lambda p: np.full(int(p.view_ptr[-1]), float(p.sigma)) if p.view_sigma is None else np.asarray(p.view_sigma, dtype=np.float64).reshape(-1)
+        vs = cat(side(a), side(b))
+    return UpdateProblem(**{**a.__dict__, "view_sigma": vs, "view_ptr": vp, "obs_uv": cat(a.obs_uv, b.obs_uv), "obs_slot": cat(a.obs_slot, b.obs_slot),
                             "idp_base": cat(a.idp_base, b.idp_base), "idp_m": cat(a.idp_m, b.idp_m), "idp_rho": cat(a.idp_rho, b.idp_rho)})
 
 

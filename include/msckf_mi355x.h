@@ -32,8 +32,9 @@
  *     pinned next to the creating thread).  Environment: MSCKF_HOST_THREADS (default 3, 0 = none), MSCKF_HOST_PAR_MIN (smallest batch that is
  *     split, default 1024 features), MSCKF_HOST_SPIN_US (how long idle workers poll before they sleep, default 1000).
  *   - waiting: msckf_update, msckf_get_result, msckf_get_covariance and msckf_sync return with the device drained of
- *     everything their results depend on; msckf_set_features, msckf_set_poses, msckf_commit_covariance and msckf_run
- *     leave their work in the context's stream (host arrays passed in are copied before the call returns).
+ *     everything their results depend on; msckf_set_features, msckf_set_poses, msckf_commit_covariance, msckf_run,
+ *     msckf_run_rows and msckf_run_fix leave their work in the context's stream (host arrays passed in are copied
+ *     before the call returns).
  *   - tuning switches of the K5 plan (diagnostics; the defaults are the measured best): MSCKF_LEAF_TARGET (leaf workgroups
  *     aimed at per batch, default 240), MSCKF_LS_BIG_BATCH (from this many features on the 60-column leaves run twelve
  *     wavefronts, default 4000), MSCKF_LS_TALL (90-column leaves with 56-row blocks, default 1; 0 = 32-row blocks).
@@ -340,6 +341,42 @@ int msckf_augment_imu(msckf_ctx* ctx);
  * IMU state, biases, every clone pose and null pose.  Same return codes; a no-op (1) or failed update (< 0) leaves P
  * and the record untouched.  Asynchronous wherever msckf_commit_covariance is. */
 int msckf_commit_inject(msckf_ctx* ctx);
+
+/* ---- direct measurement rows on the resident filter -------------------------- *
+ * Every update kernel behind K5 takes T_H = [0 | T]: camera rows, zero on the 15 IMU columns.  These calls take any
+ * other measurement -- a zero-velocity update at standstill, a position or velocity fix, a height, a pose from another
+ * estimator, a row on a bias -- without leaving the resident path: m rows H (1 <= m <= MSCKF_MAX_ROWS) over the leading
+ * n_cols of the d = 15 + 6 N error-state columns (1 <= n_cols <= d, row-major m x n_cols, the columns behind them are
+ * zero and cost nothing: n_cols = 15 is the IMU-only case), the residual r[m] and the noise matrix R[m*m]:
+ *     S = H P H^T + R = L L^T,   gamma = r^T S^-1 r,   K = P H^T S^-1,   dx = K r,
+ *     P+ = (I - K H) P (I - K H)^T + K R K^T, symmetrised              (MSCKF.py:604-607, :612-614 with R for R_n)
+ * Sign convention: r = z - h(nominal state), the measured value minus the predicted one.  Always fp64, also on an
+ * MSCKF_DTYPE_F32 context.  Two launches, asynchronous like msckf_run, and the result lands where msckf_run's does:
+ * msckf_get_result returns dx, P_out and stats (accepted may be NULL; accepted[0] is the verdict; n_features = 1,
+ * n_accepted / n_rejected = 1 / 0 or 0 / 1, stacked_rows = m), msckf_commit_covariance / msckf_commit_inject keep it.
+ * chi2_crit > 0 gates the update: it is applied iff gamma <= chi2_crit (<= 0: not gated); a NaN gamma (a non-finite r)
+ * is a rejection either way.  A rejected update is a no-op: return code 1 from the three readers, dx = 0, P_out = the
+ * prior.  A pivot of S that is not a positive normal number (R indefinite, or a non-finite H or R) is
+ * MSCKF_ERR_NOT_SPD from the readers, P and the nominal state unchanged.  Two runs on the same inputs give the same
+ * bits, and P_out is bit-symmetric.
+ * The loaded feature batch is not touched: after a rows update is committed, msckf_run is the camera update of that
+ * batch on the new P and the new poses.
+ * Errors, nothing launched: MSCKF_ERR_STATE without msckf_set_state; MSCKF_ERR_ARG for m or n_cols out of range, a
+ * null pointer, or an R that is not bitwise symmetric. */
+#define MSCKF_MAX_ROWS 32
+int msckf_run_rows(msckf_ctx* ctx, int32_t m, int32_t n_cols, const double* H, const double* r,
+                   const double* R, double chi2_crit);
+/* Three rows on the resident nominal state (msckf_set_nominal first, else MSCKF_ERR_STATE): the device forms
+ * r = z - t_WI (columns 12..14: the error state is ordered theta, b_g, v, b_a, p, as msckf_commit_inject reads dx)
+ * or r = z - v (columns 6..8) in stream order, behind whatever msckf_propagate_imu left
+ * pending, with no read-back.  z[3], R[9] (bitwise symmetric); `which` unknown: MSCKF_ERR_ARG.  A zero-velocity update is
+ * MSCKF_FIX_VELOCITY with z = 0. */
+#define MSCKF_FIX_POSITION 1
+#define MSCKF_FIX_VELOCITY 2
+int msckf_run_fix(msckf_ctx* ctx, int32_t which, const double* z, const double* R, double chi2_crit);
+/* gamma and the verdict (1 applied, 0 rejected or not SPD -- gamma is NaN then) of the last rows run; waits for it.
+ * MSCKF_ERR_STATE when the last run was not a rows run.  Either pointer may be NULL. */
+int msckf_get_rows_gate(msckf_ctx* ctx, double* gamma, int32_t* applied);
 
 /* ---- the track store: views and bases resident, batches by track id -------- *
  * The feature batch is the last input of the resident loop that depends on the clone poses: every Line.base is the

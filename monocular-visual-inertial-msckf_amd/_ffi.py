@@ -18,6 +18,8 @@ OK, NOOP = 0, 1
 ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOT_SPD, ERR_STATE, ERR_DUP_SLOT, ERR_COMM = -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
 MAX_TRACK = 31
+MAX_ROWS = 32           # MSCKF_MAX_ROWS: rows of one msckf_run_rows
+FIX_POSITION, FIX_VELOCITY = 1, 2
 MAX_TRACK_ROW = 32      # MSCKF_MAX_TRACK_ROW: views a row of the track store may hold (a batch track: MAX_TRACK)
 
 # every symbol include/msckf_mi355x.h declares
@@ -41,6 +43,7 @@ SYMBOLS = [
     "msckf_tracks_frame", "msckf_tracks_load_where", "msckf_tracks_counters", "msckf_tracks_clone_views",
     "msckf_tracks_match", "msckf_tracks_match_frame", "msckf_tracks_descriptor",
     "msckf_update_sigma", "msckf_set_view_sigma",
+    "msckf_run_rows", "msckf_run_fix", "msckf_get_rows_gate",
 ]
 
 
@@ -240,6 +243,12 @@ def load():
     for name in ("msckf_augment_imu", "msckf_commit_inject"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = C.c_int
+    lib.msckf_run_rows.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double]
+    lib.msckf_run_rows.restype = C.c_int
+    lib.msckf_run_fix.argtypes = [vp, C.c_int32, _dp, _dp, C.c_double]
+    lib.msckf_run_fix.restype = C.c_int
+    lib.msckf_get_rows_gate.argtypes = [vp, _dp, _ip]
+    lib.msckf_get_rows_gate.restype = C.c_int
     lib.msckf_tracks_reset.argtypes = [vp]
     lib.msckf_tracks_observe.argtypes = [vp, C.c_int32, _ip, _dp, _dp]
     lib.msckf_tracks_remove.argtypes = [vp, C.c_int32, _ip]

@@ -111,6 +111,7 @@ class UpdateEngine:
         self.max_clones, self.max_features, self.max_track = max_clones, max_features, max_track
         self._N = 0
         self._F = 0
+        self._rows_run = False                # the last run was run_rows / a fix: result() holds one verdict
         self._views = None      # views of the loaded batch where the caller's arrays told (set_view_sigma checks its length)
         self._desc_dim = 0      # D of the last tracks_match_frame that went in (track_descriptor trims to it)
 
@@ -233,8 +234,10 @@ class UpdateEngine:
 
     def run(self):
         self._check(self._lib.msckf_run(self._h), allow_noop=False)
+        self._rows_run = False
 
     def run_compress(self):
+        self._rows_run = False
         self._check(self._lib.msckf_run_compress(self._h), allow_noop=False)
 
     def sync(self):
@@ -243,6 +246,7 @@ class UpdateEngine:
     def run_timed(self, iters: int, stages: bool = False):
         """`iters` back-to-back device pipelines timed with HIP events on the
         engine's stream.  Returns (ms_total, [us_feature, us_qr, us_gain] or None)."""
+        self._rows_run = False
         ms = C.c_float(0)
         st = (C.c_float * 3)()
         self._check(self._lib.msckf_run_timed(self._h, iters, C.byref(ms), st if stages else None), allow_noop=False)
@@ -255,7 +259,8 @@ class UpdateEngine:
         acc = np.zeros(max(self._F, 1), dtype=np.uint8)
         st = _ffi.Stats()
         rc = self._check(self._lib.msckf_get_result(self._h, _ffi.dptr(dx), _ffi.dptr(P_out), _ffi.uptr(acc), C.byref(st)))
-        return UpdateResult(rc, dx, P_out, acc[:self._F].copy(), st.as_dict())
+        n_acc = 1 if self._rows_run else self._F       # (a rows run: one verdict, whatever batch is loaded)
+        return UpdateResult(rc, dx, P_out, acc[:n_acc].copy(), st.as_dict())
 
     def commit_covariance(self) -> int:
         return self._check(self._lib.msckf_commit_covariance(self._h))
@@ -442,6 +447,81 @@ class UpdateEngine:
     def commit_inject(self) -> int:
         """`commit_covariance` + the state injection of `MSCKF.correct` (reference `MSCKF.py:616-661`) on the device."""
         return self._check(self._lib.msckf_commit_inject(self._h))
+
+    # -- direct measurement rows on the resident filter -------------------------
+    @staticmethod
+    def _rows_noise(R, m: int) -> np.ndarray:
+        """`R` as an m x m matrix: a scalar sigma, a vector of m sigmas or the full matrix."""
+        a = np.asarray(R, dtype=np.float64)
+        if a.ndim == 0:
+            return np.eye(m) * float(a) ** 2
+        if a.ndim == 1:
+            if a.size != m:
+                raise ValueError(f"R holds {a.size} sigmas, the measurement {m} rows")
+            return np.diag(a ** 2)
+        return _ffi.f64(a)
+
+    @staticmethod
+    def _rows_crit(gate, m: int) -> float:
+        """The critical value of `gate`: False / None not gated, True `chi2_table()[m]`, a float itself."""
+        if gate is None or gate is False:
+            return 0.0
+        if gate is True:
+            return float(chi2_table()[m])
+        return float(gate)
+
+    def run_rows(self, H, r, R, gate=False):
+        """An update with the caller's rows `H` (m x n_cols, any n_cols <= d: the columns behind them are zero and are
+        not padded), residual `r = z - h(nominal)` and noise `R` (scalar sigma, m sigmas or m x m) on the resident
+        covariance; async.  The result is read by `result`, kept by `commit_covariance` / `commit_inject`.
+        `gate`: True gates at `chi2_table()[m]`, a float at that value."""
+        H = _ffi.f64(np.atleast_2d(np.asarray(H, dtype=np.float64)))
+        r = _ffi.f64(r).reshape(-1)
+        m, n_cols = (int(H.shape[0]), int(H.shape[1])) if H.size else (0, 0)
+        if r.size != m:
+            raise ValueError(f"r holds {r.size} entries, H {m} rows")
+        Rm = self._rows_noise(R, m)
+        if Rm.shape != (m, m):
+            raise ValueError(f"R is {Rm.shape}, expected ({m}, {m})")
+        self._check(self._lib.msckf_run_rows(self._h, m, n_cols, _ffi.dptr(H), _ffi.dptr(r), _ffi.dptr(Rm),
+                                             self._rows_crit(gate, m)), allow_noop=False)
+        self._rows_run = True
+
+    def update_rows(self, H, r, R, gate=False) -> UpdateResult:
+        """`run_rows` + `result`."""
+        self.run_rows(H, r, R, gate)
+        return self.result()
+
+    def _run_fix(self, which: int, z, R, gate):
+        z = _ffi.f64(z).reshape(-1)
+        if z.size != 3:
+            raise ValueError("z has 3 entries")
+        Rm = self._rows_noise(R, 3)
+        if Rm.shape != (3, 3):
+            raise ValueError(f"R is {Rm.shape}, expected (3, 3)")
+        self._check(self._lib.msckf_run_fix(self._h, which, _ffi.dptr(z), _ffi.dptr(Rm), self._rows_crit(gate, 3)),
+                    allow_noop=False)
+        self._rows_run = True
+
+    def velocity_fix(self, z, R, gate=False):
+        """A velocity measurement `z` (world frame) against the resident nominal state: the device forms `r = z - v`
+        behind whatever `propagate_imu` left pending, no read-back; async."""
+        self._run_fix(_ffi.FIX_VELOCITY, z, R, gate)
+
+    def position_fix(self, z, R, gate=False):
+        """A position measurement `z` of the IMU in the world frame: `r = z - t_WI` formed on the device; async."""
+        self._run_fix(_ffi.FIX_POSITION, z, R, gate)
+
+    def zero_velocity(self, sigma, gate=False):
+        """A zero-velocity update at standstill: `velocity_fix` with z = 0."""
+        self._run_fix(_ffi.FIX_VELOCITY, np.zeros(3), sigma, gate)
+
+    def rows_gate(self):
+        """(gamma, applied) of the last rows run; waits for it."""
+        g = np.zeros(1)
+        a = np.zeros(1, dtype=np.int32)
+        self._check(self._lib.msckf_get_rows_gate(self._h, _ffi.dptr(g), _ffi.iptr(a)), allow_noop=False)
+        return float(g[0]), bool(a[0])
 
     # -- the track store: views and bases resident, batches by track id --------
     def tracks_reset(self):
@@ -641,6 +721,7 @@ class UpdateEngine:
     def merge_gain(self, blocks, total_accepted: int, n_blocks: Optional[int] = None):
         """Root side: QR-merge the gathered blocks and run K6-K7.  `blocks` is a
         host array (G, 6N, 6N+1) or an int device address (then pass n_blocks)."""
+        self._rows_run = False
         if isinstance(blocks, (int, np.integer)):
             self._check(self._lib.msckf_run_merge_gain(self._h, C.c_void_p(int(blocks)), int(n_blocks), 1,
                                                        int(total_accepted)), allow_noop=False)
@@ -715,6 +796,7 @@ class UpdateEngine:
         """Root side: fold the shards' group triangles, one root sweep, K6-K7.  `records` is a host array
         (G, record_doubles) or an int device address (then pass n_records); `total_accepted` < 0 takes the
         sum of the counts the shards wrote into their records."""
+        self._rows_run = False
         if isinstance(records, (int, np.integer)):
             self._check(self._lib.msckf_run_merge_groups(self._h, C.c_void_p(int(records)), int(n_records), 1,
                                                          int(total_accepted)), allow_noop=False)
@@ -727,6 +809,7 @@ class UpdateEngine:
         """`merge_groups` without any device-to-host traffic: `flags` (n_records, N) uint8 says which first-slot
         groups each shard's record carries (the caller partitioned the batch, so it knows); the accepted counts
         are summed on the device.  `records_ptr` is an HBM address."""
+        self._rows_run = False
         fl = np.ascontiguousarray(flags, dtype=np.uint8)
         self._check(self._lib.msckf_run_merge_groups_flags(self._h, C.c_void_p(int(records_ptr)), int(n_records), 1,
                                                            fl.ctypes.data), allow_noop=False)

@@ -18,6 +18,7 @@
 #include <sched.h>
 #include <cmath>
 #include <cstdio>
+#include <limits>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -39,9 +40,11 @@
 #include "k_assoc.h"
 #include "k_tracks.h"
 #include "k_match.h"
+#include "k_rows.h"
 #include "run_outcome.h"
 #include "track_mirror.h"
 #include "batch_order.h"
+#include "rows_args.h"
 
 static_assert(TrackMirror::kOk == MSCKF_OK && TrackMirror::kErrArg == MSCKF_ERR_ARG && TrackMirror::kErrDupSlot == MSCKF_ERR_DUP_SLOT,
               "track_mirror.h returns the ABI's codes");
@@ -267,7 +270,7 @@ inline int host_par_min() {
 // What a run launched: everything a reader of its results needs to know.  The launchers (run_pipeline, msckf_run_merge_gain,
 // run_merge_groups) fill a local one and commit it with finish_run when every launch is in the stream; a run that returns an
 // error commits nothing.
-enum class RunKind { Pipeline, RootMerge, GroupMerge };
+enum class RunKind { Pipeline, RootMerge, GroupMerge, Rows };      // Rows: direct measurement rows (k_rows.h), no batch behind it
 enum class AccSource { Gate, Fixed, Word2 };     // the accepted count: the gate results' sum, `accepted`, status word 2 (summed on the device)
 struct RunRecord {
     bool ran = false;                     // a run was committed and nothing has voided its results since
@@ -281,6 +284,7 @@ struct RunRecord {
     bool streamed_gain = false;           // pipeline: K6-K7 was k_gain_stream (fused or a launch of its own)
     bool fused_root = false;              // pipeline: ... in the root sweep's launch (k_root_gain: stage events cannot split it)
     bool fused_leaves = false;            // pipeline: ... and the leaves with them (k_leaf_root_gain)
+    int rows_m = 0;                       // rows: the measurement's row count (msckf_stats.stacked_rows)
     long serial = 0;                      // finish_run numbers the runs
 };
 
@@ -505,6 +509,9 @@ struct msckf_ctx {
     bool desc_ready = false;
     int desc_D = 0;                       // the store's descriptor dimension; 0: not set yet
     PinStage trk_match_stage, trk_desc_stage;
+    // direct measurement rows (k_rows.h): H | r | R go up as one pinned image; Y and the slabs' partial S live behind them
+    Buf dRows;
+    PinStage rows_stage;
     long fetched_serial = -1;             // the run whose return code msckf_get_result derived last ...
     int fetched_rc = 0;                   // ... and that code: msckf_commit_covariance need not read the gate results again
 };
@@ -1903,6 +1910,98 @@ bool take_fake_timeout(msckf_ctx* c) {
     return true;
 }
 
+// ---- direct measurement rows (k_rows.h) --------------------------------------------------------------------------
+// gamma of a rows run sits behind the five status words in the head of the result range, on the device and in its mirror
+constexpr size_t ROWS_GATE_OFF = 48;
+
+// The rows run's status words, from the mirror its second launch wrote (seeded with 3 by run_rows): waits for the stream.
+int rows_status_words(msckf_ctx* c, int status[5]) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->feat_busy = c->pose_busy = c->main_busy = c->run_pending = false;
+    std::memcpy(status, c->hRes, 20);
+    status[1] = status[3] = status[4] = 0;       // (not this run's)
+    return MSCKF_OK;
+}
+
+int rows_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted, msckf_stats* st) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const double t0 = now_us();
+    const size_t d = c->d;
+    const RunRecord& r = c->last;
+    char* hres = static_cast<char*>(c->hRes);
+    // dx | P_out behind the status head: the head's mirror is the launch's own and is not overwritten
+    if (dx || P_out) {
+        const size_t bytes = (P_out ? c->res_p_off + d * d * 8 : c->res_dx_off + d * 8) - c->res_dx_off;
+        HIPCHK(c, hipMemcpyAsync(hres + c->res_dx_off, static_cast<char*>(c->dResArena.p) + c->res_dx_off, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    int status[5], n_acc;
+    if (int rc0 = rows_status_words(c, status)) return rc0;
+    const int rc = outcome_rc(c, run_outcome(r, status, 0, &n_acc));
+    if (accepted) accepted[0] = rc == MSCKF_OK ? 1 : 0;
+    if (dx) {
+        if (rc == MSCKF_OK) std::memcpy(dx, hres + c->res_dx_off, d * 8);
+        else std::memset(dx, 0, d * 8);
+    }
+    if (P_out) {
+        if (rc == MSCKF_OK) { if (c->pool) c->pool->copy(P_out, hres + c->res_p_off, d * d * 8); else std::memcpy(P_out, hres + c->res_p_off, d * d * 8); }
+        else HIPCHK(c, hipMemcpy(P_out, c->dP.p, d * d * 8, hipMemcpyDeviceToHost));       // rejected or failed: the prior
+    }
+    c->us_d2h = (float)(now_us() - t0);
+    c->fetched_serial = r.serial; c->fetched_rc = rc;
+    if (st) {
+        std::memset(st, 0, sizeof(*st));
+        st->n_features = 1; st->n_accepted = rc == MSCKF_OK ? 1 : 0; st->n_rejected = rc == MSCKF_NOOP ? 1 : 0;
+        st->stacked_rows = r.rows_m;
+        st->us_d2h = c->us_d2h;
+    }
+    return rc;
+}
+
+// m rows over the leading n_cols columns.  rz: the residual, or (nom_off >= 0) the measured value whose residual against the
+// resident nominal record the device forms in stream order, behind whatever msckf_propagate_imu left pending.
+int run_rows(msckf_ctx* c, int m, int n_cols, const double* H, const double* rz, const double* R, double chi2_crit, int nom_off) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = c->d, nt = (d + 15) / 16, nsl = (n_cols + 15) / 16;
+    const size_t dcap = 15 + 6 * (size_t)c->maxN, ntcap = (dcap + 15) / 16;
+    const size_t up_cap = (size_t)ROWS_MAX * dcap + ROWS_MAX + ROWS_MAX * ROWS_MAX;              // H | r | R
+    const size_t o_r = (size_t)m * n_cols, o_R = o_r + ROWS_MAX, o_Y = up_cap, o_S = o_Y + ntcap * 16 * ROWS_MAX;
+    if (int rc = ensure(c, c->dRows, (o_S + ntcap * ROWS_MAX * ROWS_MAX) * 8)) return rc;
+    PinStage& ps = c->rows_stage;
+    if (!ps.p) {
+        HIPCHK(c, hipHostMalloc(&ps.p, up_cap * 8));
+        ps.cap = up_cap * 8;
+        HIPCHK(c, hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
+    }
+    if (ps.pending) { HIPCHK(c, hipEventSynchronize(ps.ev)); ps.pending = false; }       // (the previous image's copy is through)
+    double* h = static_cast<double*>(ps.p);
+    std::memcpy(h, H, o_r * 8);
+    std::memcpy(h + o_r, rz, (size_t)m * 8);
+    std::memcpy(h + o_R, R, (size_t)m * m * 8);
+    double* dv = ptr<double>(c->dRows);
+    HIPCHK(c, hipMemcpyAsync(dv, h, (o_R + (size_t)m * m) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(ps.ev, c->stream));
+    ps.pending = true;
+    if (c->state_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_state, 0)); c->state_pending = false; }
+    RowsArgs a{};
+    a.P = ptr<double>(c->dP); a.ldp = d; a.d = d; a.m = m; a.n_cols = n_cols; a.nsl = nsl;
+    a.H = dv; a.rz = dv + o_r; a.R = dv + o_R;
+    a.nom = nom_off >= 0 ? ptr<double>(c->dNom) : nullptr; a.nom_off = nom_off;
+    a.crit = chi2_crit > 0.0 ? chi2_crit : std::numeric_limits<double>::infinity();
+    a.Y = dv + o_Y; a.Spart = dv + o_S;
+    a.dx = ptr<double>(c->dDx); a.Pout = ptr<double>(c->dPout); a.ldo = d;
+    a.status = ptr<int>(c->dStatus); a.gate = reinterpret_cast<double*>(static_cast<char*>(c->dStatus.p) + ROWS_GATE_OFF);
+    a.status_h = static_cast<int*>(c->hRes); a.gate_h = reinterpret_cast<double*>(static_cast<char*>(c->hRes) + ROWS_GATE_OFF);
+    a.status_h[0] = 3; a.status_h[2] = 0;            // 3: not written
+    hipLaunchKernelGGL(k_rows_y, dim3(nt), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_rows_update, dim3(nt, nt), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    RunRecord rec;
+    rec.kind = RunKind::Rows; rec.gain = true; rec.acc = AccSource::Word2; rec.rows_m = m;
+    finish_run(c, rec);
+    c->main_busy = true;
+    return MSCKF_OK;
+}
+
 int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     if (!c->have_state || !c->have_features) return MSCKF_ERR_STATE;
     int rc;
@@ -2355,7 +2454,7 @@ void msckf_destroy(msckf_ctx* c) {
                   &c->dFlush, &c->dFlushOff, &c->dFeatInfo, &c->dCommBuf, &c->dAssocUV, &c->dAssocRes,
                   &c->dGsEx, &c->dGsFlag, &c->dGsProg, &c->dMProg, &c->dMFlush, &c->dRootFlush, &c->dXRootFlush,
                   &c->dSplit, &c->dRem, &c->dNom, &c->dTrk, &c->dTrkRows, &c->dTrkRowSorted,
-                  &c->dDescViews, &c->dDescRow, &c->dMatch};
+                  &c->dDescViews, &c->dDescRow, &c->dMatch, &c->dRows};
     for (Buf* b : all) if (b->p && !b->view) (void)hipFree(b->p);
     for (Buf* b : {&c->dPoseArena, &c->dFeatArena, &c->dRawArena, &c->dResArena, &c->dGateArena, &c->dPlanArena}) if (b->p) (void)hipFree(b->p);
     for (void* h : {c->hPose, c->hFeat, c->hRes, c->hGate, c->hP}) if (h) (void)hipHostFree(h);
@@ -2368,7 +2467,7 @@ void msckf_destroy(msckf_ctx* c) {
     for (void* h : c->hPlan) if (h) (void)hipHostFree(h);
     if (c->ev_state) (void)hipEventDestroy(c->ev_state);
     if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
-    for (PinStage* ps : {&c->trk_obs_stage, &c->trk_load_stage, &c->trk_frame_stage, &c->trk_match_stage, &c->trk_desc_stage}) {
+    for (PinStage* ps : {&c->trk_obs_stage, &c->trk_load_stage, &c->trk_frame_stage, &c->trk_match_stage, &c->trk_desc_stage, &c->rows_stage}) {
         if (ps->ev) (void)hipEventDestroy(ps->ev);
         if (ps->p) (void)hipHostFree(ps->p);
     }
@@ -2841,6 +2940,7 @@ int msckf_get_result(msckf_ctx* c, double* dx, double* P_out, uint8_t* accepted,
     if (!c) return MSCKF_ERR_ARG;
     if (!c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->last.kind == RunKind::Rows) return rows_get_result(c, dx, P_out, accepted, st);
     const double t0 = now_us();
     const size_t d = c->d;
     const RunRecord& r = c->last;
@@ -2922,6 +3022,17 @@ int msckf_commit_covariance(msckf_ctx* c) {
         if (c->fetched_rc != MSCKF_OK) return c->fetched_rc;
         HIPCHK(c, hipMemcpyAsync(c->dP.p, c->dPout.p, (size_t)c->d * c->d * 8, hipMemcpyDeviceToDevice, c->stream));
         c->main_busy = true;                           // (stays in the stream: every reader of P is behind it)
+        return MSCKF_OK;
+    }
+    if (c->last.kind == RunKind::Rows) {                // no batch decides a rows run: its launch mirrored the verdict
+        int rows_status[5];
+        if (int rc0 = rows_status_words(c, rows_status)) return rc0;
+        int n_rows_acc;
+        const int rc = outcome_rc(c, run_outcome(c->last, rows_status, 0, &n_rows_acc));
+        c->fetched_serial = c->last.serial; c->fetched_rc = rc;
+        if (rc != MSCKF_OK) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->dP.p, c->dPout.p, (size_t)c->d * c->d * 8, hipMemcpyDeviceToDevice, c->stream));
+        c->main_busy = true;
         return MSCKF_OK;
     }
     int counters[4] = {0, 0, 0, 0};
@@ -3426,6 +3537,38 @@ int msckf_commit_inject(msckf_ctx* c) {
     hipLaunchKernelGGL(k_inject, dim3((c->N + 1 + 63) / 64), dim3(64), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     c->main_busy = true;
+    return MSCKF_OK;
+}
+
+// ---- direct measurement rows on the resident filter (k_rows.h) ---------------------------------------------------
+int msckf_run_rows(msckf_ctx* c, int32_t m, int32_t n_cols, const double* H, const double* r, const double* R, double chi2_crit) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->have_state) return MSCKF_ERR_STATE;
+    if (!rows_args_ok(m, n_cols, c->d, H, r, R)) return MSCKF_ERR_ARG;
+    return run_rows(c, m, n_cols, H, r, R, chi2_crit, -1);
+}
+
+int msckf_run_fix(msckf_ctx* c, int32_t which, const double* z, const double* R, double chi2_crit) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->have_state || !c->have_nominal) return MSCKF_ERR_STATE;
+    if (which != MSCKF_FIX_POSITION && which != MSCKF_FIX_VELOCITY) return MSCKF_ERR_ARG;
+    // the error state's order is theta, b_g, v, b_a, p (k_inject: t += dx[12..14], v += dx[6..8])
+    const int col0 = which == MSCKF_FIX_POSITION ? 12 : 6, n_cols = col0 + 3;
+    if (!rows_args_ok(3, n_cols, c->d, z, z, R)) return MSCKF_ERR_ARG;
+    double H[3 * 15] = {0};
+    for (int i = 0; i < 3; ++i) H[i * n_cols + col0 + i] = 1.0;
+    return run_rows(c, 3, n_cols, H, z, R, chi2_crit, which == MSCKF_FIX_POSITION ? NOM_T : NOM_V);
+}
+
+int msckf_get_rows_gate(msckf_ctx* c, double* gamma, int32_t* applied) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->last.ran || c->last.kind != RunKind::Rows) return MSCKF_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    int status[5];
+    if (int rc = rows_status_words(c, status)) return rc;
+    if (status[0] == 3) { c->last_error = "the rows update did not report a status"; return MSCKF_ERR_HIP; }
+    if (gamma) std::memcpy(gamma, static_cast<const char*>(c->hRes) + ROWS_GATE_OFF, 8);
+    if (applied) *applied = (status[0] == 0 && status[2] == 1) ? 1 : 0;
     return MSCKF_OK;
 }
 

@@ -17,7 +17,7 @@ elif kind == "ragged":
 else:
     prob = synth.make_problem(N, F, M, seed=0)
 with UpdateEngine(max_clones=N, max_features=F, max_track=M, dtype=dtype) as eng:
-    if "SPLIT_DIRECT_ROWS" in os.environ:          # remainder rows taken as they are up to this many (default 2048 / 16384)
+    if "SPLIT_DIRECT_ROWS" in os.environ:          # remainder rows taken as they are up to this many (default 3840; 16384 on windows of more than 31 clones)
         eng.set_rem_direct_rows(int(os.environ["SPLIT_DIRECT_ROWS"]))
     eng.load(prob)
     for _ in range(2):

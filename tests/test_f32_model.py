@@ -108,7 +108,7 @@ def _budget(family, key, k, products, first=0):
     if family == "f":
         probs, refs = cases.sequence(key, k)
         b, per = fm.budget_sequence(probs, refs, products, first=first)
-        return b                                                       # [(b_dx, b_P)] per step
+        return [x[:2] for x in b]                                      # [(b_dx, b_P)] per step
     prob, ref = _problem(family, key, k)
     if ref["status"] != 0:
         return None

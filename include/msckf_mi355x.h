@@ -233,7 +233,8 @@ typedef struct msckf_select_params {
     int32_t min_frames_tracked;     /* MSCKFParameters.min_number_of_frames_to_be_tracked (clamped >= 2, MSCKF.py:120) */
     int32_t use_parallax;           /* MSCKFParameters.use_parallax                                       */
     int32_t width, height;          /* Camera.width / .height (Camera.py:24-25)                           */
-    int32_t reserved;
+    int32_t refine_iters;           /* 0: off (the reference's linear point).  1..32: refine the triangulated point on the
+                                       device, at most this many Levenberg-Marquardt trials (below); else MSCKF_ERR_ARG */
     double min_parallax_deg;        /* MSCKFParameters.min_parallax                                       */
     double K[9];                    /* Camera.K, row-major (Camera.py:20)                                 */
 } msckf_select_params;
@@ -241,6 +242,7 @@ typedef struct msckf_select_params {
 #define MSCKF_SEL_VALID 1           /* in valid_features: goes into the update          (MSCKF.py:492) */
 #define MSCKF_SEL_LOST 2            /* in lost_features: the caller removes it afterwards (:468, :493)  */
 #define MSCKF_SEL_REFRESHED 4       /* inverse-depth point was re-estimated              (:484-488)     */
+#define MSCKF_SEL_REFINED 8         /* ... from the refined point (refine_iters > 0), not the linear one */
 
 /* Per-view Feature.lines (line_base / line_dir 3*sumM, line_conf sumM; lines[i] belongs to
  * keypoints[i], MSCKF.py:410) and per-feature lost_for_n_frames / tracked_for_n_frames (F). */
@@ -260,6 +262,26 @@ int msckf_clear_selection(msckf_ctx* ctx);
  * idp_rho[F] as they stand after the refresh, world[F*3] = triangulated point (NaN when the
  * feature was not triangulated; the reference's estimated_world_points, MSCKF.py:489). */
 int msckf_get_selection(msckf_ctx* ctx, uint8_t* flags, double* idp_m, double* idp_rho, double* world);
+/* Refinement of the triangulated points (msckf_select_params.refine_iters > 0; a second launch behind the selection
+ * kernel, fp64 in both dtypes).  intersection_of_lines meets Feature.lines, which were stored with the pose each clone had
+ * when the view was added; the update linearises about the RESIDENT poses.  For every track flagged MSCKF_SEL_VALID and
+ * MSCKF_SEL_REFRESHED the device minimises c(x) = sum_i w_i |z_i - zhat_i(x)|^2 over x = (alpha, beta, rho), the
+ * inverse-depth point in the anchor clone a = obs_slot[first view], under the resident poses:
+ *     h_i = R_s^T (R_a [alpha, beta, 1]^T + rho (t_a - t_s)),  zhat_i = h_xy / h_z,  z_i = K^-1 [u, v, 1] dehomogenised,
+ *     w_i = line_conf[i] -- the weights of the linear step; the per-view noise of msckf_set_view_sigma is NOT used here.
+ * Levenberg-Marquardt from the linear point C = R_a^T (world - t_a), x0 = (C_x / C_z, C_y / C_z, 1 / C_z), attempted iff
+ * C_z > 0 and every h_z > 0 at x0; lambda0 = 1e-3, (A + lambda diag A) d = g with A = sum w J^T J, g = sum w J^T e; a
+ * trial is accepted iff every h_z > 0, it is finite and its cost is strictly smaller (then lambda <- max(lambda / 10,
+ * 1e-12), stop when max|d| <= 1e-9 max(1, max|x|); else lambda <- 10 lambda, stop when lambda > 1e8); at most
+ * refine_iters trials.  W = t_a + R_a [alpha, beta, 1]^T / rho is kept iff a trial was accepted, rho > 0 and W passes the
+ * anchor in-image test of the linear point; then world <- W, idp_m / idp_rho are refreshed from W exactly as from the
+ * linear point, and MSCKF_SEL_REFINED is set.  A track that is not kept stays as the linear step left it, and bits 1, 2, 4
+ * never depend on refine_iters: the plan, msckf_replan and the update's feature set are those of refine_iters = 0, and the
+ * write-back to the track store persists the refined point like any refreshed one.
+ * msckf_get_select_refine: per track in input order (any pointer may be NULL) cost0 = c at the linear point, cost1 = c at
+ * the result (= cost0 when it was not kept), trials; zeros for a track that was not attempted, and for all of them when the
+ * last selection ran with refine_iters == 0.  MSCKF_ERR_STATE without a selection.  Waits for the kernels. */
+int msckf_get_select_refine(msckf_ctx* ctx, double* cost0, double* cost1, int32_t* trials);
 
 /* ---- f4: geometric consistency tests of the front end's matches ----------------- *
  * Replaces the per-(match, earlier view) loop of MSCKF.add_camera_measurements (MSCKF.py:332-412): the
@@ -623,8 +645,8 @@ int msckf_debug_compressed(msckf_ctx* ctx, double* T, double* rn);
 /* Diagnostics: out == NULL enables per-node cycle stamps in the fold kernel; otherwise copies
  * 8 int64 per tree node {setup, staging, steps, total (100 MHz ticks), w, rows, -, -}. */
 int msckf_debug_fold_stamps(msckf_ctx* ctx, long long* out, int32_t max_nodes);
-/* Average device time of the selection kernel (HIP events, `iters` re-launches of the last
- * msckf_run_select; the kernel is idempotent). */
+/* Average device time of the selection (HIP events, `iters` re-launches of the last msckf_run_select -- the selection
+ * kernel and, with refine_iters > 0, the refinement behind it; both are idempotent). */
 int msckf_debug_time_select(msckf_ctx* ctx, int32_t iters, float* us_per_launch);
 /* How the current batch's long tracks (more than 10 clone slots) were planned: out[0] long tracks that were split
  * (two-level nullspace basis), out[1] their narrow blocks, out[2] rows their remainder blocks may hold,

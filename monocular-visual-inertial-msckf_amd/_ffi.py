@@ -30,7 +30,7 @@ SYMBOLS = [
     "msckf_export_block", "msckf_run_merge_gain", "msckf_set_group_exchange", "msckf_band_rule", "msckf_group_record_doubles",
     "msckf_export_groups", "msckf_run_merge_groups", "msckf_run_merge_groups_flags", "msckf_export_result", "msckf_import_covariance", "msckf_debug_gate", "msckf_debug_gate_codes", "msckf_debug_compressed", "msckf_debug_fold_stamps",
     "msckf_device_pointer", "msckf_stream",
-    "msckf_set_tracks", "msckf_run_select", "msckf_clear_selection", "msckf_get_selection",
+    "msckf_set_tracks", "msckf_run_select", "msckf_clear_selection", "msckf_get_selection", "msckf_get_select_refine",
     "msckf_debug_time_select", "msckf_replan", "msckf_run_associate",
     "msckf_propagate", "msckf_augment", "msckf_remove_clones", "msckf_set_poses", "msckf_get_covariance",
     "msckf_comm_unique_id", "msckf_comm_init", "msckf_comm_destroy", "msckf_comm_gather", "msckf_comm_broadcast",
@@ -84,7 +84,7 @@ DESC_DIM = 64           # floats a stored descriptor row holds: desc_dim is 1..6
 
 class SelectParamsC(C.Structure):
     _fields_ = [("min_frames_lost", C.c_int32), ("min_frames_tracked", C.c_int32), ("use_parallax", C.c_int32),
-                ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("refine_iters", C.c_int32),
                 ("min_parallax_deg", C.c_double), ("K", C.c_double * 9)]
 
 
@@ -97,7 +97,7 @@ class NominalC(C.Structure):
 
 
 IMU_BATCH_MAX = 64      # MSCKF_IMU_BATCH_MAX: samples of one msckf_propagate_imu
-SEL_VALID, SEL_LOST, SEL_REFRESHED = 1, 2, 4
+SEL_VALID, SEL_LOST, SEL_REFRESHED, SEL_REFINED = 1, 2, 4, 8
 
 _lib = None
 
@@ -222,6 +222,8 @@ def load():
     lib.msckf_clear_selection.restype = C.c_int
     lib.msckf_get_selection.argtypes = [vp, _up, _dp, _dp, _dp]
     lib.msckf_get_selection.restype = C.c_int
+    lib.msckf_get_select_refine.argtypes = [vp, _dp, _dp, _ip]
+    lib.msckf_get_select_refine.restype = C.c_int
     lib.msckf_run_associate.argtypes = [vp, C.POINTER(AssocParamsC), _dp, _up, _ip]
     lib.msckf_run_associate.restype = C.c_int
     lib.msckf_propagate.argtypes = [vp, _dp, _dp]

@@ -50,7 +50,7 @@ class UpdateResult:
 @dataclass
 class Selection:
     """Outcome of `get_valid_features` (reference `MSCKF.py:458-495`), input order."""
-    flags: np.ndarray        # (F,) uint8: 1 valid, 2 lost, 4 inverse-depth point refreshed
+    flags: np.ndarray        # (F,) uint8: 1 valid, 2 lost, 4 inverse-depth point refreshed, 8 ... from the refined point
     idp_m: np.ndarray        # (F, 3) after the refresh
     idp_rho: np.ndarray      # (F,)
     world: np.ndarray        # (F, 3) triangulated points, NaN where none
@@ -66,6 +66,11 @@ class Selection:
     @property
     def refreshed(self) -> np.ndarray:
         return (self.flags & _ffi.SEL_REFRESHED) > 0
+
+    @property
+    def refined(self) -> np.ndarray:
+        """Tracks whose point is the refined one (`SelectParams.refine_iters` > 0), a subset of `refreshed`."""
+        return (self.flags & _ffi.SEL_REFINED) > 0
 
 
 def exchange_split_rule(prob: UpdateProblem, shards, lib=None, handle=None) -> dict:
@@ -275,11 +280,15 @@ class UpdateEngine:
 
     def run_select(self, params: SelectParams, K):
         """Enqueue `get_valid_features` on the device; the following `run()` processes only
-        the valid features, with their inverse-depth points refreshed in HBM."""
+        the valid features, with their inverse-depth points refreshed in HBM.
+        `params.refine_iters` in 1..32 adds the refinement of the triangulated points under the resident poses
+        (at most that many Levenberg-Marquardt trials; `Selection.refined`, `select_refine_stats`); 0 is the
+        reference's linear point; anything else raises `EngineError` (`ERR_ARG`)."""
         sp = _ffi.SelectParamsC()
         sp.min_frames_lost, sp.min_frames_tracked = int(params.min_frames_lost), int(params.min_frames_tracked)
         sp.use_parallax, sp.width, sp.height = int(bool(params.use_parallax)), int(params.width), int(params.height)
         sp.min_parallax_deg = float(params.min_parallax_deg)
+        sp.refine_iters = int(params.refine_iters)
         sp.K = (C.c_double * 9)(*np.asarray(K, dtype=np.float64).reshape(9))
         self._check(self._lib.msckf_run_select(self._h, C.byref(sp)), allow_noop=False)
 
@@ -298,8 +307,19 @@ class UpdateEngine:
                     allow_noop=False)
         return Selection(fl[:F].copy(), m[:F].copy(), rho[:F].copy(), w[:F].copy())
 
+    def select_refine_stats(self) -> dict:
+        """Per track of the last `run_select`, input order: `cost0` the weighted reprojection cost (normalised image
+        coordinates, weights `line_conf`) at the linear point, `cost1` at the result (= `cost0` where the refined point
+        was not kept), `trials`.  Zeros for tracks that were not attempted, and everywhere after a selection with
+        `refine_iters` 0.  `EngineError` (`ERR_STATE`) without a selection."""
+        F = self._F
+        c0, c1, tr = np.zeros(max(F, 1)), np.zeros(max(F, 1)), np.zeros(max(F, 1), dtype=np.int32)
+        self._check(self._lib.msckf_get_select_refine(self._h, _ffi.dptr(c0), _ffi.dptr(c1), _ffi.iptr(tr)), allow_noop=False)
+        return {"cost0": c0[:F].copy(), "cost1": c1[:F].copy(), "trials": tr[:F].copy()}
+
     def time_select(self, iters: int = 50) -> float:
-        """Average device microseconds of the selection kernel (HIP events)."""
+        """Average device microseconds of the selection (HIP events): the selection kernel and, with `refine_iters`
+        > 0, the refinement launch behind it."""
         us = C.c_float(0)
         self._check(self._lib.msckf_debug_time_select(self._h, iters, C.byref(us)), allow_noop=False)
         return float(us.value)
@@ -989,13 +1009,16 @@ class UpdateEngine:
         inject_state(filt.state, res.dx)                                              # MSCKF.py:616-661
         return 0
 
-    def process_features(self, filt, view_sigma=None) -> int:
+    def process_features(self, filt, view_sigma=None, refine_iters: int = 0) -> int:
         """Drop-in for `MSCKF.process_features()` (reference `MSCKF.py:450-456`):
         `get_valid_features(self.features)` and `update(valid_features)` in one device pass,
         then `remove_features(lost_features)` through the filter's own method.  Mutates the
         features' inverse-depth points (`:488`) and the filter like the reference does.
         `view_sigma`: as in `update`, keyed like `filt.features`.
+        `refine_iters`: 0 the reference's linear triangulation; 1..32 refines each triangulated point on the device
+        under the current clone poses before the update (`run_select`); the features then carry the refined points.
         Returns 0 updated / 1 no-op."""
+        import dataclasses
         from .pack import problem_from_reference, select_params_from_reference, tracks_from_reference, view_sigma_from_reference
         from .inject import inject_state
         feats = filt.features
@@ -1006,7 +1029,7 @@ class UpdateEngine:
             prob.view_sigma = view_sigma_from_reference(feats, view_sigma, prob.sigma)
         self.load(prob)
         self.set_tracks(tracks_from_reference(feats))
-        self.run_select(select_params_from_reference(filt), prob.K)
+        self.run_select(dataclasses.replace(select_params_from_reference(filt), refine_iters=int(refine_iters)), prob.K)
         sel = self.selection()
         if 0 < int(sel.valid.sum()) < 0.15 * len(feats):
             self.replan()                      # few valid candidates: a shallower QR tree pays for the sync
@@ -1028,31 +1051,33 @@ class UpdateEngine:
         filt.remove_features({k: ft for j, (k, ft) in enumerate(items) if sel.flags[j] & _ffi.SEL_LOST})   # :456
         return res.status
 
-    def prune_poorest_camera_states(self, filt) -> int:
+    def prune_poorest_camera_states(self, filt, refine_iters: int = 0) -> int:
         """Drop-in for `MSCKF.prune_poorest_camera_states()` (reference `MSCKF.py:710-737`): the two clones seen by
         the fewest features, the features seen by them -> `get_valid_features` -> `update` -> `remove_cameras`,
-        composed on the resident engine (`_prune`).  Returns 0 updated / 1 no update."""
+        composed on the resident engine (`_prune`).  `refine_iters` as in `process_features`.  Returns 0 updated / 1 no update."""
         count = {}
         for ft in filt.features.values():                                             # :712-716
             for ci in ft.camera_indices:
                 count[ci] = count.get(ci, 0) + 1
         poorest = [k for k, _ in sorted(count.items(), key=lambda kv: kv[1])][:2]     # :718-724 (stable sort, dict order)
-        return self._prune(filt, {k: filt.state.cameras[k] for k in poorest})
+        return self._prune(filt, {k: filt.state.cameras[k] for k in poorest}, refine_iters)
 
-    def prune_camera_states(self, filt) -> int:
+    def prune_camera_states(self, filt, refine_iters: int = 0) -> int:
         """Drop-in for `MSCKF.prune_camera_states()` (reference `MSCKF.py:663-680`): every
         `int(max_number_of_camera_states / camera_states_to_delete)`-th clone of the window (position i > 0 with
         i % step == 0, `:665-667`), the features seen by them -> `get_valid_features` -> `update` ->
-        `remove_cameras`, composed on the resident engine (`_prune`).  Returns 0 updated / 1 no update."""
+        `remove_cameras`, composed on the resident engine (`_prune`).  `refine_iters` as in `process_features`.
+        Returns 0 updated / 1 no update."""
         step = int(filt.max_number_of_camera_states / filt.camera_states_to_delete)   # :666
         drop = {k: cam for i, (k, cam) in enumerate(filt.state.cameras.items()) if i > 0 and i % step == 0}
-        return self._prune(filt, drop)
+        return self._prune(filt, drop, refine_iters)
 
-    def _prune(self, filt, drop) -> int:
+    def _prune(self, filt, drop, refine_iters: int = 0) -> int:
         """Shared tail of the reference's two pruning methods (`MSCKF.py:669-680`, `:726-737`): selection, update,
         commit and the removal of the clones' rows / columns (`:751-757`) run back to back in HBM; the covariance
         crosses PCIe once in each direction.  The dictionary bookkeeping of `remove_cameras` (`:758-777`, including
         the `last_camera_measurement` entries of features that lost all their views) stays on the host."""
+        import dataclasses
         from .pack import problem_from_reference, select_params_from_reference, tracks_from_reference
         from .inject import inject_state
         cams = filt.state.cameras
@@ -1064,7 +1089,7 @@ class UpdateEngine:
             prob = problem_from_reference(filt, todo)
             self.load(prob)
             self.set_tracks(tracks_from_reference(todo))
-            self.run_select(select_params_from_reference(filt), prob.K)
+            self.run_select(dataclasses.replace(select_params_from_reference(filt), refine_iters=int(refine_iters)), prob.K)
             sel = self.selection()
             items = list(todo.items())
             for j, (_, ft) in enumerate(items):

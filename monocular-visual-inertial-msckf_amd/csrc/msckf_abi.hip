@@ -317,6 +317,9 @@ struct msckf_ctx {
     Buf dNodes, dRbuf, dStamps, dSweepNodes, dSweepFolds;
     Buf dPlanArena;                       // the plan's tables in one allocation (upload_plan): dNodes, dSweepNodes, dSweepFolds, dRootFlush, dFlush, dFlushOff are views
     Buf dLineBase, dLineDir, dLineConf, dLostFor, dTrackedFor, dSelFlags, dWorld;   // f1 (k_select)
+    Buf dSelRefine;                       // k_select_refine's diagnostics, allocated by the first refining selection: cost0 [cap] | cost1 [cap] | trials [cap]
+    int sel_refine_cap = 0;               // tracks dSelRefine holds
+    bool sel_refined = false;             // the last msckf_run_select launched k_select_refine
     Buf dY, dS, dL, dU, dInvd, dK, dB2, dD, dPn, dDx, dCholWork, dStatus;
     // host-side plan
     BatchOrder ord;                       // the current batch in the pipeline's order (batch_order.h); valid under have_features
@@ -2450,7 +2453,7 @@ void msckf_destroy(msckf_ctx* c) {
                   &c->dObsUV, &c->dObsSlot, &c->dBase, &c->dMvec, &c->dRho, &c->dFmin, &c->dBlkOff, &c->dStack,
                   &c->dRank, &c->dAcc, &c->dGamma, &c->dKeep, &c->dNodes, &c->dRbuf, &c->dStamps, &c->dSweepNodes, &c->dSweepFolds, &c->dY, &c->dS, &c->dL,
                   &c->dU, &c->dInvd, &c->dK, &c->dB2, &c->dD, &c->dPn, &c->dDx, &c->dCholWork, &c->dStatus,
-                  &c->dLineBase, &c->dLineDir, &c->dLineConf, &c->dLostFor, &c->dTrackedFor, &c->dSelFlags, &c->dWorld,
+                  &c->dLineBase, &c->dLineDir, &c->dLineConf, &c->dLostFor, &c->dTrackedFor, &c->dSelFlags, &c->dWorld, &c->dSelRefine,
                   &c->dFlush, &c->dFlushOff, &c->dFeatInfo, &c->dCommBuf, &c->dAssocUV, &c->dAssocRes,
                   &c->dGsEx, &c->dGsFlag, &c->dGsProg, &c->dMProg, &c->dMFlush, &c->dRootFlush, &c->dXRootFlush,
                   &c->dSplit, &c->dRem, &c->dNom, &c->dTrk, &c->dTrkRows, &c->dTrkRowSorted,
@@ -3180,9 +3183,15 @@ int msckf_set_tracks(msckf_ctx* c, const double* line_base, const double* line_d
 int msckf_run_select(msckf_ctx* c, const msckf_select_params* sp) {
     if (!c || !sp) return MSCKF_ERR_ARG;
     if (!c->have_state || !c->have_features || !c->have_tracks) return MSCKF_ERR_STATE;
-    if (sp->width < 1 || sp->height < 1) return MSCKF_ERR_ARG;
+    if (sp->width < 1 || sp->height < 1 || sp->refine_iters < 0 || sp->refine_iters > 32) return MSCKF_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    if (sp->refine_iters > 0 && c->F > c->sel_refine_cap) {
+        const int cap = std::max(c->F, c->cfg.max_features);
+        if (int rc = ensure(c, c->dSelRefine, (size_t)cap * 20)) return rc;
+        c->sel_refine_cap = cap;
+    }
     c->use_select = true;
+    c->sel_refined = sp->refine_iters > 0 && c->F > 0;
     c->last.ran = false;
     c->sel_params = *sp;
     if (c->F == 0) return MSCKF_OK;
@@ -3200,6 +3209,18 @@ int msckf_run_select(msckf_ctx* c, const msckf_select_params* sp) {
     a.flags = ptr<unsigned char>(c->dSelFlags); a.idp_m = ptr<double>(c->dMvec); a.idp_rho = ptr<double>(c->dRho);
     a.world = ptr<double>(c->dWorld);
     hipLaunchKernelGGL(k_select, dim3((c->F * 8 + 255) / 256), dim3(256), 0, c->stream, a);
+    if (sp->refine_iters > 0) {                             // the refined point under the resident poses
+        SelectRefineArgs r{};
+        r.F = c->F; r.iters = sp->refine_iters;
+        r.view_ptr = a.view_ptr; r.obs_slot = a.obs_slot; r.obs_uv = ptr<double>(c->dObsUV); r.line_conf = a.line_conf;
+        r.cam_R = a.cam_R; r.cam_t = a.cam_t;
+        std::memcpy(r.K, a.K, 72); std::memcpy(r.Kinv, a.Kinv, 72);
+        r.width = a.width; r.height = a.height;
+        r.flags = a.flags; r.idp_m = a.idp_m; r.idp_rho = a.idp_rho; r.world = a.world;
+        r.cost0 = ptr<double>(c->dSelRefine); r.cost1 = r.cost0 + c->sel_refine_cap;
+        r.trials = reinterpret_cast<int*>(r.cost1 + c->sel_refine_cap);
+        hipLaunchKernelGGL(k_select_refine, dim3((c->F * 8 + 255) / 256), dim3(256), 0, c->stream, r);
+    }
     if (c->batch_from_store)                                // the reference's refresh persists (MSCKF.py:488)
         hipLaunchKernelGGL(k_track_writeback, dim3((c->F + 255) / 256), dim3(256), 0, c->stream, c->trk, c->F,
                            (const unsigned char*)a.flags, (const double*)a.idp_m, (const double*)a.idp_rho,
@@ -3279,6 +3300,34 @@ int msckf_get_selection(msckf_ctx* c, uint8_t* flags, double* idp_m, double* idp
         if (idp_rho) idp_rho[f] = hr[s];
         if (idp_m) std::memcpy(&idp_m[(size_t)f * 3], &hm[(size_t)s * 3], 24);
         if (world) std::memcpy(&world[(size_t)f * 3], &hw[(size_t)s * 3], 24);
+    }
+    return MSCKF_OK;
+}
+
+int msckf_get_select_refine(msckf_ctx* c, double* cost0, double* cost1, int32_t* trials) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->use_select) return MSCKF_ERR_STATE;
+    const int F = c->F;
+    if (F == 0) return MSCKF_OK;
+    if (!c->sel_refined) {                                  // refine_iters == 0: nothing was attempted
+        if (cost0) std::memset(cost0, 0, (size_t)F * 8);
+        if (cost1) std::memset(cost1, 0, (size_t)F * 8);
+        if (trials) std::memset(trials, 0, (size_t)F * 4);
+        return MSCKF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<double> h0(F), h1(F);
+    std::vector<int> ht(F);
+    const double* d0 = ptr<double>(c->dSelRefine);
+    HIPCHK(c, hipMemcpyAsync(h0.data(), d0, (size_t)F * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h1.data(), d0 + c->sel_refine_cap, (size_t)F * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ht.data(), d0 + 2 * (size_t)c->sel_refine_cap, (size_t)F * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int s = 0; s < F; ++s) {
+        const int f = c->ord.perm[s];
+        if (cost0) cost0[f] = h0[s];
+        if (cost1) cost1[f] = h1[s];
+        if (trials) trials[f] = ht[s];
     }
     return MSCKF_OK;
 }

@@ -103,6 +103,7 @@ class SelectParams:
     min_parallax_deg: float = 20.0
     width: int = WIDTH
     height: int = HEIGHT
+    refine_iters: int = 0             # not the reference's: 1..32 refines the triangulated point on the device
 
 
 @dataclass

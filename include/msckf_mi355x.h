@@ -202,7 +202,10 @@ int msckf_set_state(msckf_ctx* ctx, int32_t N, const double* P,
                     const double* gravity, const double* Kinv, double sigma,
                     const double* chi2_crit, int32_t n_crit);
 /* Upload one feature batch (the `features` dict of MSCKF.update): sorts the
- * tracks by first slot, plans the QR tree and copies everything to HBM. */
+ * tracks by first slot, plans the QR tree and copies everything to HBM.
+ * The batch replaces the previous one, gate results included, so the call voids the
+ * results of the last run (a rows run too): read and commit a run BEFORE the next
+ * batch is loaded; behind it msckf_get_result and both commits return MSCKF_ERR_STATE. */
 int msckf_set_features(msckf_ctx* ctx, int32_t F, const int32_t* view_ptr,
                        const double* obs_uv, const int32_t* obs_slot,
                        const double* idp_base, const double* idp_m,
@@ -361,7 +364,10 @@ int msckf_propagate_imu(msckf_ctx* ctx, int32_t n, const double* gyro, const dou
 int msckf_augment_imu(msckf_ctx* ctx);
 /* msckf_commit_covariance, then MSCKF.correct's state injection (MSCKF.py:616-661) of this update's dx, read from HBM:
  * IMU state, biases, every clone pose and null pose.  Same return codes; a no-op (1) or failed update (< 0) leaves P
- * and the record untouched.  Asynchronous wherever msckf_commit_covariance is. */
+ * and the record untouched.  Asynchronous wherever msckf_commit_covariance is.
+ * A run is injected ONCE: a second msckf_commit_inject of the same run returns MSCKF_ERR_STATE and touches neither P nor
+ * the record (its dx would be added to the IMU state, the biases and every pose again).  msckf_commit_covariance stays
+ * repeatable -- it copies the same P_out --, in front of msckf_commit_inject (which then injects once) and behind it. */
 int msckf_commit_inject(msckf_ctx* ctx);
 
 /* ---- direct measurement rows on the resident filter -------------------------- *

@@ -200,6 +200,8 @@ class UpdateEngine:
             self._h, prob.N, _ffi.dptr(a["P"]), _ffi.dptr(a["cam_R"]), _ffi.dptr(a["cam_t"]), _ffi.dptr(a["cam_R0"]),
             _ffi.dptr(a["cam_t0"]), _ffi.dptr(a["g"]), _ffi.dptr(a["Kinv"]), float(prob.sigma), _ffi.dptr(chi),
             int(chi.size)), allow_noop=False)
+        if prob.N != self._N:                 # (another N drops the loaded batch; at the same N it stays, and so does its size)
+            self._F = 0
         self._N = prob.N
 
     def set_features(self, prob: UpdateProblem):
@@ -368,7 +370,6 @@ class UpdateEngine:
                              view_ptr=np.zeros(1, dtype=np.int32), obs_uv=np.zeros((0, 2)),
                              obs_slot=np.zeros(0, dtype=np.int32), idp_base=z3, idp_m=z3, idp_rho=np.zeros(0))
         self.set_state(prob)
-        self._F = 0
 
     def propagate(self, Phi, Q):
         """Covariance half of `process_imu` (reference `MSCKF.py:236-244`); async."""
@@ -465,7 +466,8 @@ class UpdateEngine:
         self._F = 0
 
     def commit_inject(self) -> int:
-        """`commit_covariance` + the state injection of `MSCKF.correct` (reference `MSCKF.py:616-661`) on the device."""
+        """`commit_covariance` + the state injection of `MSCKF.correct` (reference `MSCKF.py:616-661`) on the device.
+        A run is injected once: a second call for the same run raises `EngineError` (`ERR_STATE`) and changes nothing."""
         return self._check(self._lib.msckf_commit_inject(self._h))
 
     # -- direct measurement rows on the resident filter -------------------------

@@ -285,6 +285,7 @@ struct RunRecord {
     bool fused_root = false;              // pipeline: ... in the root sweep's launch (k_root_gain: stage events cannot split it)
     bool fused_leaves = false;            // pipeline: ... and the leaves with them (k_leaf_root_gain)
     int rows_m = 0;                       // rows: the measurement's row count (msckf_stats.stacked_rows)
+    bool injected = false;                // msckf_commit_inject added this run's dx to the nominal state: a run is injected once
     long serial = 0;                      // finish_run numbers the runs
 };
 
@@ -3578,6 +3579,9 @@ int msckf_augment_imu(msckf_ctx* c) {
 int msckf_commit_inject(msckf_ctx* c) {
     if (!c) return MSCKF_ERR_ARG;
     if (!c->have_nominal) return MSCKF_ERR_STATE;
+    // the dx of a run is added once: a second injection would move the IMU state, the biases and every clone pose again
+    // (msckf_commit_covariance behind it stays legal: it copies the same P_out)
+    if (c->last.ran && c->last.injected) return MSCKF_ERR_STATE;
     const int rc = msckf_commit_covariance(c);
     if (rc != MSCKF_OK) return rc;        // no-op or failed update: P and the record stay as they are
     InjectArgs a{};
@@ -3585,6 +3589,7 @@ int msckf_commit_inject(msckf_ctx* c) {
     a.camR = ptr<double>(c->dCamR); a.camT = ptr<double>(c->dCamT); a.camR0 = ptr<double>(c->dCamR0); a.camT0 = ptr<double>(c->dCamT0);
     hipLaunchKernelGGL(k_inject, dim3((c->N + 1 + 63) / 64), dim3(64), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
+    c->last.injected = true;
     c->main_busy = true;
     return MSCKF_OK;
 }

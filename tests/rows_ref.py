@@ -80,32 +80,38 @@ def _full_noise(rng, s, f):
     return np.diag(s) @ (A @ A.T / 3.0 + f * f * np.eye(s.size)) @ np.diag(s)
 
 
-def measurement(case, k=None):
-    """(P, H, r, R) of a case; H is m x n_cols."""
-    P = np.array(fp.filter_prior(case.N)[0])
+def rows_on(P, kind, m, rng, f=0.5):
+    """(H, r, R) of a measurement of `kind` with m rows on ANY prior P, sized in units of sqrt(diag P) as the table above says;
+    H is m x n_cols.  `measurement` is this on filter_prior(N); tests/call_sequences.py calls it on the P a sequence holds."""
     d = P.shape[0]
     s = np.sqrt(np.diag(P))
-    rng = np.random.default_rng([case_seed(case, k), case.m])
-    f = NOISE_FACTOR.get(case.name, 0.5)
-    if case.kind in ("zupt", "pos", "tpos"):
-        c0 = {"zupt": 6, "pos": 3, "tpos": 12}[case.kind]
+    if kind in ("zupt", "pos", "tpos"):
+        c0 = {"zupt": 6, "pos": 3, "tpos": 12}[kind]
         H = np.zeros((3, c0 + 3))
         H[:, c0:] = np.eye(3)
-        R = np.diag((f * s[c0:c0 + 3]) ** 2) if case.kind == "zupt" else _full_noise(rng, s[c0:c0 + 3], f)
-    elif case.kind == "clone":
+        R = np.diag((f * s[c0:c0 + 3]) ** 2) if kind == "zupt" else _full_noise(rng, s[c0:c0 + 3], f)
+    elif kind == "clone":
         H = np.zeros((6, d))
         H[:, d - 6:] = np.eye(6)
         R = _full_noise(rng, s[d - 6:], f)
-    elif case.kind == "imu":
-        H = rng.standard_normal((case.m, 15))
-        R = np.diag((0.3 * (np.abs(H) @ s[:15])) ** 2 * rng.uniform(0.5, 2.0, case.m))
+    elif kind == "imu":
+        H = rng.standard_normal((m, 15))
+        R = np.diag((0.3 * (np.abs(H) @ s[:15])) ** 2 * rng.uniform(0.5, 2.0, m))
     else:
-        H = rng.standard_normal((case.m, d)) / s[None, :]
-        R = np.diag(np.einsum("ij,jk,ik->i", H, P, H) * rng.uniform(0.25, 4.0, case.m))
+        H = rng.standard_normal((m, d)) / s[None, :]
+        R = np.diag(np.einsum("ij,jk,ik->i", H, P, H) * rng.uniform(0.25, 4.0, m))
     R = (R + R.T) / 2                       # bitwise symmetric, as the ABI asks
     Hd = pad(H, d)
     S = Hd @ P @ Hd.T + R
-    r = np.linalg.cholesky((S + S.T) / 2) @ rng.standard_normal(case.m)
+    r = np.linalg.cholesky((S + S.T) / 2) @ rng.standard_normal(H.shape[0])
+    return H, r, R
+
+
+def measurement(case, k=None):
+    """(P, H, r, R) of a case; H is m x n_cols."""
+    P = np.array(fp.filter_prior(case.N)[0])
+    rng = np.random.default_rng([case_seed(case, k), case.m])
+    H, r, R = rows_on(P, case.kind, case.m, rng, NOISE_FACTOR.get(case.name, 0.5))
     return P, H, r, R
 
 

@@ -1066,6 +1066,20 @@ def main():
         return synth.UpdateProblem(**{**prob.__dict__, "P": P}), None
     cases["edge_gauge_prior"] = gauge_prior
     cases["edge_few_rows_long_tracks"] = lambda: (synth.make_problem(20, 5, 18, seed=45, variable_tracks=True, min_track=14), None)   # m << 6N
+
+    # Camera geometries other than synth.clone_poses' corridor (tests/geometry_cases.py): every fixture above looks along world +x
+    # and moves along its optical axis, and the one with rank(H_f) = 2 has tracks of at most 4 views.  These pin the oracle's
+    # view_terms and its rank-2 null space to the reference off the corridor and on long tracks.
+    def geometry(name, **override):
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import geometry_cases as gc
+        return (gc.make_case(gc.CASES[name], **override), None)
+    cases["edge_geometry_rotated_world"] = lambda: geometry("rotated_k24")          # world axes and gravity turned, distinct null poses
+    cases["edge_geometry_inward_arc"] = lambda: geometry("arc_k32")                 # half a circle looking inward, tracks of 11 - 15 views
+    # rank 2, every track: 16 - 31 views on 31 clones.  (A diagonal prior: four dense 201 x 201 arrays do not fit the size a
+    # committed file may have, and what this fixture pins -- H_f, its null space, the gate's dof 2M - 2 -- does not depend on it)
+    cases["edge_geometry_pure_rotation"] = lambda: geometry("rotation_split", views=(16, 31), F=40,
+                                                            P=np.diag(np.random.default_rng(46).uniform(0.5e-3, 2e-3, 15 + 6 * 31)))
     if args.headline:
         cases["cfg3_A"] = lambda: (synth.make_problem(30, 2000, 10, seed=0), None)
 

@@ -76,10 +76,19 @@ extern "C" {
 #define MSCKF_DTYPE_F64 0
 #define MSCKF_DTYPE_F32 1
 
-#define MSCKF_MAX_TRACK 31          /* views per feature (2M+1 rows fit one wavefront)      */
+#define MSCKF_MAX_TRACK 31          /* views of a track the NARROW K1-K4 kernels take (k_feature: one lane per measurement
+                                       row, 2M+1 rows fit one wavefront); longer tracks go to k_feature_wide            */
 #define MSCKF_MAX_TRACK_ROW 32      /* views a row of the track store may hold: a track of MSCKF_MAX_TRACK views can take
-                                       the newest clone's view (msckf_tracks_frame); a batch track still holds at most
-                                       MSCKF_MAX_TRACK                                        */
+                                       the newest clone's view (msckf_tracks_frame); on a context created with
+                                       max_track <= MSCKF_MAX_TRACK_ROW a batch track still holds at most MSCKF_MAX_TRACK */
+#define MSCKF_MAX_TRACK_WIDE 64     /* views of a batch track on a context created with max_track > MSCKF_MAX_TRACK_ROW
+                                       (fp64 only).  k_feature_wide keeps, per workgroup, the track's D, V, Z, r rows and the
+                                       packed lower triangle of the gate matrix with the residual row in LDS:
+                                       2 V^2 + 43.5 V + 1105 doubles at V views = 12081 doubles = 94.4 KiB at 64 (the
+                                       160 KiB of a CU would hold V = 88).  64 is where the other holders of a track end:
+                                       k_gather walks a track in two passes of 32 lanes, k_fold's leaves map a track's
+                                       slots through 64 words per wavefront, and the gate's strip holds 8 tiles of 16
+                                       columns of S (2 V - rank <= 128 rows) in accumulators                            */
 
 typedef struct msckf_ctx msckf_ctx;
 
@@ -88,8 +97,12 @@ typedef struct msckf_config {
     int32_t device;                 /* HIP device ordinal                                   */
     int32_t max_clones;             /* capacity: N  (<= 221, else MSCKF_ERR_ARG)            */
     int32_t max_features;           /* capacity: F                                          */
-    int32_t max_track;              /* capacity: M  (<= MSCKF_MAX_TRACK; MSCKF_MAX_TRACK_ROW gives the track store
-                                       rows of that many views, the batch limit stays MSCKF_MAX_TRACK) */
+    int32_t max_track;              /* capacity: M  (<= MSCKF_MAX_TRACK_WIDE, else MSCKF_ERR_ARG).  Up to MSCKF_MAX_TRACK: the
+                                       batch limit.  MSCKF_MAX_TRACK_ROW: the track store's rows hold that many views, the
+                                       batch limit stays MSCKF_MAX_TRACK.  More: the batch limit (fp64; an f32 context keeps
+                                       MSCKF_MAX_TRACK), tracks of more than MSCKF_MAX_TRACK views take k_feature_wide and the
+                                       merge tree; such a context has no track store (msckf_tracks_*: MSCKF_ERR_ARG) and
+                                       a batch with such a track takes no part in a sharded update (MSCKF_ERR_STATE)   */
     int32_t leaf_rows;              /* 0 = default; target stacked rows per QR leaf         */
     int32_t merge_arity;            /* 0 = default; max children per QR tree node           */
     int32_t flags;                  /* MSCKF_FLAG_*; 0 = defaults                           */

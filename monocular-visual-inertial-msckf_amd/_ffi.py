@@ -21,6 +21,7 @@ MAX_TRACK = 31
 MAX_ROWS = 32           # MSCKF_MAX_ROWS: rows of one msckf_run_rows
 FIX_POSITION, FIX_VELOCITY = 1, 2
 MAX_TRACK_ROW = 32      # MSCKF_MAX_TRACK_ROW: views a row of the track store may hold (a batch track: MAX_TRACK)
+MAX_TRACK_WIDE = 64     # MSCKF_MAX_TRACK_WIDE: views of a batch track on a context created with max_track > MAX_TRACK_ROW (fp64)
 
 # every symbol include/msckf_mi355x.h declares
 SYMBOLS = [

@@ -99,8 +99,10 @@ class UpdateEngine:
         dtype: "f64" = the reference's arithmetic (parity 1e-8); "f32" = fp32 storage of the stacked system and
         the Joseph covariance update on the f32 matrix cores (BASELINE.json configs[4]; tolerance in DESIGN.md)."""
         self._lib = _ffi.load()
-        if max_track > _ffi.MAX_TRACK_ROW:               # (MAX_TRACK + 1: rows of the track store only, a batch track holds MAX_TRACK)
-            raise ValueError(f"max_track {max_track} > {_ffi.MAX_TRACK_ROW}")
+        # (up to MAX_TRACK: the batch limit; MAX_TRACK_ROW: rows of the track store only, a batch track holds MAX_TRACK; beyond: the
+        #  batch limit of a context without a track store, tracks of more than MAX_TRACK views on the wide K1-K4 kernel)
+        if max_track > _ffi.MAX_TRACK_WIDE:
+            raise ValueError(f"max_track {max_track} > {_ffi.MAX_TRACK_WIDE}")
         if plan not in ("auto", "band", "tree"):
             raise ValueError("plan must be 'auto', 'band' or 'tree'")
         if dtype not in ("f64", "f32"):

@@ -88,13 +88,16 @@ __global__ __launch_bounds__(256) void k_tri_gather(TriGatherArgs p) {
 
 constexpr int FOLD_MAX_SRC = 1024;   // sources per node the LDS bookkeeping can hold
 constexpr int STAGE_U = 4;           // loads in flight per lane while a leaf stages one K4 block
+// a leaf's wavefront maps the views of the track it stages to window columns through FOLD_SLOTMAP_LD words of its own: the most
+// views a track may hold (MSCKF_MAX_TRACK_WIDE).  The layouts below reserve 16 * 32 words: eight wavefronts (T <= 512)
+constexpr int FOLD_SLOTMAP_LD = 64;
 
 // LDS carve-up of k_fold (offsets in doubles); shared by the kernel and the host planner.
 struct FoldLayout {
     int ld;        // staging row stride (odd: conflict-free column walks)
     int vbuf;      // [2][bmax + 2] published column j (+ pivot)
     int ints;      // int region: nalive[w], rstate[w], srow0[FOLD_MAX_SRC+1], ctl[8], blead[bmax],
-                   //             bsrc[bmax], slotmap[16][32]
+                   //             bsrc[bmax], slotmap[8][64]
     int panel;     // [prow][ld] staging panel
     int prow;      // staging rows that fit
 };
@@ -118,6 +121,7 @@ __global__ __launch_bounds__(T) void k_fold_g(FoldArgs p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int NCG = T / 16;          // column groups
     constexpr int BMAX = 16 * RPT;       // rows per register batch
+    static_assert((T / 64) * FOLD_SLOTMAP_LD <= 16 * 32, "slot maps of the wavefronts: fold_layout reserves 16 * 32 words");
     const FoldNode nd = p.nodes[p.node_base + blockIdx.x];
     const int t = threadIdx.x;
     const int rq = t & 15;               // row lane inside the DPP row
@@ -134,7 +138,7 @@ __global__ __launch_bounds__(T) void k_fold_g(FoldArgs p) {
     int* s_ctl = srow0 + (FOLD_MAX_SRC + 1);                  // [8]
     int* blead = s_ctl + 8;                                   // [BMAX] leading column of each batch row
     int* bsrc = blead + BMAX;                                 // [BMAX] merge: (child << 20) | child row
-    int* slotmap = bsrc + BMAX;                               // [T/64][32] leaf: per-wave clone slots of a track
+    int* slotmap = bsrc + BMAX;                               // [T/64][64] leaf: per-wave clone slots of a track (up to 64 views)
     double* panel = smem + lay.panel;                         // [prow][ld]
 
     double* out = p.rbuf + nd.out_off;
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(T) void k_fold_g(FoldArgs p) {
                 __syncthreads();
                 // one wavefront per source block (column-major (6M+1) x 2M)
                 const int wv = t >> 6, ln = t & 63;
-                int* smap = slotmap + wv * 32;
+                int* smap = slotmap + wv * FOLD_SLOTMAP_LD;
                 for (int i = wv; i < nfold; i += T / 64) {
                     const int r0 = srow0[i], r1 = srow0[i + 1];
                     if (r1 <= sub_lo || r0 >= sub_lo + np || r1 == r0) continue;
@@ -460,6 +464,7 @@ __global__ __launch_bounds__(T) void k_fold(FoldArgs p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int NCG = T / RL;          // column groups
     constexpr int BMAX = RL * RPT;       // rows per register batch
+    static_assert((T / 64) * FOLD_SLOTMAP_LD <= 16 * 32, "slot maps of the wavefronts: fold_layout_r reserves 16 * 32 words");
     const FoldNode nd = p.nodes[p.node_base + blockIdx.x];
     const int t = threadIdx.x;
     const int rq = t & (RL - 1);         // row lane inside the half DPP row
@@ -474,7 +479,7 @@ __global__ __launch_bounds__(T) void k_fold(FoldArgs p) {
     int* s_ctl = srow0 + (FOLD_MAX_SRC + 1);                  // [8]
     int* blead = s_ctl + 8;                                   // [BMAX] leading column of each batch row
     int* bsrc = blead + BMAX;                                 // [BMAX] merge: (child << 20) | child row
-    int* slotmap = bsrc + BMAX;                               // [T/64][32] leaf: per-wave clone slots of a track
+    int* slotmap = bsrc + BMAX;                               // [T/64][64] leaf: per-wave clone slots of a track (up to 64 views)
     double* racc = smem + lay.racc;                           // packed R accumulator
     double* panel = smem + lay.panel;                         // [prow][ld] leaf staging panel
     const int nracc = (w + 1) * (w + 2) / 2;
@@ -541,7 +546,7 @@ __global__ __launch_bounds__(T) void k_fold(FoldArgs p) {
                 for (int e = t; e < np * ld; e += T) panel[e] = 0.0;
                 __syncthreads();
                 const int wv = t >> 6, ln = t & 63;
-                int* smap = slotmap + wv * 32;
+                int* smap = slotmap + wv * FOLD_SLOTMAP_LD;
                 for (int i = wv; i < nfold; i += T / 64) {
                     const int r0 = srow0[i], r1 = srow0[i + 1];
                     if (r1 <= sub_lo || r0 >= sub_lo + np || r1 == r0) continue;

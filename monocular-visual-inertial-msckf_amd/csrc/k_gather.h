@@ -67,12 +67,21 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather(GatherArgs p) {
         *reinterpret_cast<double2*>(p.uv + 2 * (size_t)(o + v)) = q;
         p.slot[o + v] = sl;
     }
-    int lo = sl;
+    // (a wide track, 33 - 64 views: the group's second pass takes the views from 32 on)
+    int sl2 = 1 << 30;
+    if (v + 32 < M) {
+        sl2 = p.slot_in[a + v + 32];
+        const double2 q = *reinterpret_cast<const double2*>(p.uv_in + 2 * (size_t)(a + v + 32));
+        *reinterpret_cast<double2*>(p.uv + 2 * (size_t)(o + v + 32)) = q;
+        p.slot[o + v + 32] = sl2;
+    }
+    int lo = min(sl, sl2);
 #pragma unroll
     for (int k = 16; k >= 1; k >>= 1) lo = min(lo, __shfl_xor(lo, k, 32));
     if (v < 2) scol[grp][v] = ~0ull;
     __syncthreads();
     if (v < M && sl - lo < 16) reinterpret_cast<unsigned char*>(scol[grp])[sl - lo] = (unsigned char)v;
+    if (v + 32 < M && sl2 - lo < 16) reinterpret_cast<unsigned char*>(scol[grp])[sl2 - lo] = (unsigned char)(v + 32);
     __syncthreads();
     if (!live) return;
     if (v < 3) p.base[3 * (size_t)s + v] = hv;

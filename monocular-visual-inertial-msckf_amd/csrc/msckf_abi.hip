@@ -26,6 +26,7 @@
 
 #include "../../include/msckf_mi355x.h"
 #include "k_feature.h"
+#include "k_feature_wide.h"
 #include "k_fold.h"
 #include "k_gain.h"
 #include "k_gstream.h"
@@ -324,6 +325,9 @@ struct msckf_ctx {
     Buf dY, dS, dL, dU, dInvd, dK, dB2, dD, dPn, dDx, dCholWork, dStatus;
     // host-side plan
     BatchOrder ord;                       // the current batch in the pipeline's order (batch_order.h); valid under have_features
+    std::vector<int> wide_list;           // sorted indices of the batch's wide tracks (more than MSCKF_MAX_TRACK views: k_feature_wide), ascending
+    int narrow_mmax = 0;                  // most views of the other tracks of such a batch
+    size_t wide_list_off = 0;             // the list in the raw image (pinned and in HBM), bytes from its head
     std::vector<FoldNode> nodes;
     std::vector<std::pair<int, int>> levels;   // (node_base, count) per fold launch
     int root = -1;
@@ -657,6 +661,7 @@ void invalidate_batch(msckf_ctx* c) {
 // blocks a small dense QR beside it.  Any window size, both dtypes.  Under the group exchange of a sharded update only with
 // split records (msckf_set_exchange_split: the remainder rows ride in the record); never where a plan is forced.
 // (which tracks those are, and how they are cut: batch_order.h)
+static_assert(FEATW_MAXM == MSCKF_MAX_TRACK_WIDE && MSCKF_MAX_TRACK_WIDE <= FOLD_SLOTMAP_LD, "k_feature_wide, k_fold's leaves and the ABI name one limit");
 static_assert(kOrderOk == MSCKF_OK && kOrderErrArg == MSCKF_ERR_ARG && kOrderErrDupSlot == MSCKF_ERR_DUP_SLOT, "batch_order.h returns the ABI's codes");
 // the sequential block update (k_gstream.h) on DENSE rows at this window size: strips and LDS
 bool gstream_fits(int dc) {
@@ -1431,6 +1436,17 @@ int launch_feature(msckf_ctx* c) {
         } else {
             go(0, c->ord.Fb, c->ord.Mmax_band); go_split(c->ord.Fb, c->ord.Fw, c->ord.Mmax_wide);
         }
+    } else if (!c->wide_list.empty()) {
+        // tracks of more than MSCKF_MAX_TRACK views: one workgroup of k_feature_wide each, by the list of their sorted indices; the
+        // others exactly as ever, in the runs of the sorted order that lie between them
+        int s0 = 0;
+        for (int wi : c->wide_list) { go(s0, wi - s0, c->narrow_mmax); s0 = wi + 1; }
+        go(s0, c->F - s0, c->narrow_mmax);
+        FeatureWideArgs wa{};
+        a.f0 = 0; a.F = (int)c->wide_list.size(); a.split = nullptr;
+        wa.a = a;
+        wa.list = reinterpret_cast<const int*>(static_cast<const char*>(c->dRawArena.p) + c->wide_list_off);
+        hipLaunchKernelGGL(k_feature_wide, dim3((unsigned)c->wide_list.size()), dim3(FEATW_T), FEATW_LDS_BYTES, st, wa);
     } else go(0, c->F, c->ord.Mmax);
     HIPCHK(c, hipGetLastError());
     return MSCKF_OK;
@@ -2260,7 +2276,7 @@ int msckf_device_count(void) {
 
 int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     if (!out || !cfg || cfg->abi_version != MSCKF_ABI_VERSION) return MSCKF_ERR_ARG;
-    if (cfg->max_track < 1 || cfg->max_track > MSCKF_MAX_TRACK_ROW || cfg->max_clones < 1 || cfg->max_features < 0)
+    if (cfg->max_track < 1 || cfg->max_track > MSCKF_MAX_TRACK_WIDE || cfg->max_clones < 1 || cfg->max_features < 0)
         return MSCKF_ERR_ARG;
     if (cfg->dtype != MSCKF_DTYPE_F64 && cfg->dtype != MSCKF_DTYPE_F32) return MSCKF_ERR_ARG;
     int n = 0;
@@ -2268,7 +2284,10 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     msckf_ctx* c = new msckf_ctx();
     c->cfg = *cfg;
     c->device = cfg->device;
-    c->maxN = cfg->max_clones; c->maxF = cfg->max_features; c->maxM = std::min<int>(cfg->max_track, MSCKF_MAX_TRACK); c->maxV = cfg->max_track;
+    c->maxN = cfg->max_clones; c->maxF = cfg->max_features; c->maxV = cfg->max_track;
+    // a batch track: up to MSCKF_MAX_TRACK views on the narrow kernels; a context created for more (fp64) takes up to max_track
+    // of them on k_feature_wide.  (MSCKF_MAX_TRACK_ROW sizes the rows of the track store only; the f32 stack has no wide kernel)
+    c->maxM = (cfg->max_track > MSCKF_MAX_TRACK_ROW && cfg->dtype == MSCKF_DTYPE_F64) ? cfg->max_track : std::min<int>(cfg->max_track, MSCKF_MAX_TRACK);
     if (hipSetDevice(c->device) != hipSuccess) { delete c; return MSCKF_ERR_NO_DEVICE; }
     hipDeviceProp_t prop{};
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) { delete c; return MSCKF_ERR_NO_DEVICE; }
@@ -2352,6 +2371,7 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     lds_attr(reinterpret_cast<const void*>(&k_feature<24>), LDS_MAX_BYTES - 1024, "k_feature LDS attribute");
     lds_attr(reinterpret_cast<const void*>(&k_feature<32>), LDS_MAX_BYTES - 1024, "k_feature LDS attribute");
     lds_attr(reinterpret_cast<const void*>(&k_feature<64>), LDS_MAX_BYTES - 1024, "k_feature LDS attribute");
+    lds_attr(reinterpret_cast<const void*>(&k_feature_wide), (int)FEATW_LDS_BYTES, "k_feature_wide LDS attribute");
     // k_propagate keeps T = Phi P[:15, :] (15 x d) + a 15 x 15 block in LDS
     if (((size_t)15 * (15 + 6 * c->maxN) + 225) * 8 > (size_t)(LDS_MAX_BYTES - 1024)) { msckf_destroy(c); return MSCKF_ERR_ARG; }
     lds_attr(reinterpret_cast<const void*>(&k_propagate), LDS_MAX_BYTES - 1024, "k_propagate LDS attribute");
@@ -2555,6 +2575,7 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     c->no_wide = false;
     c->have_w = false;                    // the weights belonged to the batch that is gone
     c->gather_rec = nullptr;
+    c->wide_list.clear(); c->narrow_mmax = 0;
     if (F == 0) {
         c->F = 0;
         c->sumM = 0; c->ord.reset(); c->nodes.clear(); c->levels.clear(); c->snodes.clear(); c->sfolds.clear(); c->sweep_levels.clear(); c->n_group_merges = 0;
@@ -2587,14 +2608,19 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     if (view_ptr[0] != 0) return MSCKF_ERR_ARG;
     // the CSR offsets first, all of them (a few microseconds): the feature ranges below read obs_slot[view_ptr[f] ..] and must
     // not do so through an offset no earlier range has vouched for (a malformed view_ptr would send them out of bounds)
+    bool has_wide = false;                               // a track of more than MSCKF_MAX_TRACK views (maxM allows it): k_feature_wide
     for (int f = 0; f < F; ++f) {
         const int M = view_ptr[f + 1] - view_ptr[f];
         if (M < 1 || M > c->maxM) return MSCKF_ERR_ARG;
+        has_wide |= M > MSCKF_MAX_TRACK;
     }
+    if (has_wide && c->xchg) { c->last_error = "a track of more than MSCKF_MAX_TRACK views takes no part in a sharded update"; return MSCKF_ERR_STATE; }
     const int sumM = view_ptr[F];
     const RawLayout raw = raw_layout(F, sumM);           // (input order; the sort's records behind the arrays)
-    // (behind the image, in both memories: room for one weight per view -- msckf_set_view_sigma may bring them later)
-    const size_t w_off = (raw.pin_bytes + 15) & ~(size_t)15, img_bytes = w_off + (size_t)sumM * 8;
+    // (behind the image, in both memories: room for one weight per view -- msckf_set_view_sigma may bring them later -- and, in a
+    //  batch with wide tracks, for the list of them)
+    const size_t w_off = (raw.pin_bytes + 15) & ~(size_t)15, wl_off = (w_off + (size_t)sumM * 8 + 15) & ~(size_t)15;
+    const size_t img_bytes = has_wide ? wl_off + (size_t)F * 4 : w_off + (size_t)sumM * 8;
     if (c->hFeatCap < img_bytes) {
         if (c->hFeat) HIPCHK(c, hipHostFree(c->hFeat));
         c->hFeat = nullptr; c->hFeatCap = 0;
@@ -2622,7 +2648,8 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     // the code), and the range's share of the remaining arrays into the pinned image
     // key = (class, first slot, last slot); class 0: tracks of up to WIDE_SPAN clone slots (and long ones that cannot be split:
     // views out of slot order, more than SPLIT_MAXG groups, more views than k_feature<64> holds); class 2: long tracks, split
-    const bool split = split_ok(c, N);
+    // (a batch with a wide track splits none: every track keeps one block, and the batch one plan on the merge tree)
+    const bool split = split_ok(c, N) && !has_wide;
     std::vector<int> key_in(F);
     std::vector<unsigned char> M_in(F);
     ScanPart tot;
@@ -2697,6 +2724,18 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     const size_t split_off = raw.split_off(Fs);
     if (ord.split_on) std::memcpy(hb + split_off, ord.h_split.data(), ord.h_split.size() * sizeof(SplitRec));
     c->h_view_in.assign(view_ptr, view_ptr + F + 1);
+    if (has_wide) {
+        // the wide tracks' places in the sorted order, beside the order itself: k_feature_wide takes them by this list, the
+        // narrow kernels the runs between them (launch_feature)
+        int* hl = reinterpret_cast<int*>(hb + wl_off);
+        for (int s = 0; s < F; ++s) {
+            const int M = h_view[s + 1] - h_view[s];
+            if (M > MSCKF_MAX_TRACK) { hl[c->wide_list.size()] = s; c->wide_list.push_back(s); }
+            else c->narrow_mmax = std::max(c->narrow_mmax, M);
+        }
+        c->wide_list_off = wl_off;
+        HIPCHK(c, hipMemcpyAsync(draw + wl_off, hb + wl_off, c->wide_list.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
     const double ts = now_us(), t1 = ts;
 
     // sorted image (what the kernels read), written by k_gather: Fs entries, sumMs views
@@ -2867,6 +2906,7 @@ static int replan_current(msckf_ctx* c, bool one_plan) {
 
 int msckf_run_compress(msckf_ctx* c) {
     if (!c) return MSCKF_ERR_ARG;
+    if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     if (c->have_features && c->wide_active && !c->xchg_planned) {
         // the compressed block leaves this context (msckf_export_block): one plan for every track, the wide ones included
@@ -3642,12 +3682,14 @@ static int tracks_load_rows(msckf_ctx* c, int F, const std::vector<int>& rows, c
 }
 
 int msckf_tracks_reset(msckf_ctx* c) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c) return MSCKF_ERR_ARG;
     tracks_clear(c);
     return MSCKF_OK;
 }
 
 int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const double* uv, const double* score) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || n < 0) return MSCKF_ERR_ARG;
     if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
     if (n == 0) return MSCKF_OK;
@@ -3676,6 +3718,7 @@ int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const doub
 }
 
 int msckf_tracks_remove(msckf_ctx* c, int32_t n, const int32_t* ids) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || n < 0 || (n > 0 && !ids)) return MSCKF_ERR_ARG;
     if (int rc = c->mirror.remove(ids, n)) return rc;
     tracks_rows_freed(c, (size_t)n);
@@ -3683,6 +3726,7 @@ int msckf_tracks_remove(msckf_ctx* c, int32_t n, const int32_t* ids) {
 }
 
 int msckf_tracks_load(msckf_ctx* c, int32_t F, const int32_t* ids, const int32_t* lost_for, const int32_t* tracked_for) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || F < 0 || F > c->maxF) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     if (F > 0 && (!ids || !lost_for || !tracked_for)) return MSCKF_ERR_ARG;
@@ -3745,6 +3789,7 @@ static int tracks_frame_impl(msckf_ctx* c, const msckf_frame_params* fp, int32_t
 
 int msckf_tracks_frame(msckf_ctx* c, const msckf_frame_params* fp, int32_t n, const int32_t* ids, const double* uv,
                        const double* score, uint8_t* result, int32_t* fail_view) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     return tracks_frame_impl(c, fp, n, ids, uv, score, result, fail_view, false);
 }
 
@@ -3809,6 +3854,7 @@ static int match_run(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const f
 }
 
 int msckf_tracks_match(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, int32_t* track_id_out, float* sim_out) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || n < 0 || (n > 0 && !track_id_out)) return MSCKF_ERR_ARG;
     if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
     std::vector<int> rows, pair;
@@ -3825,6 +3871,7 @@ int msckf_tracks_match(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const
 
 int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t n, const float* desc, const double* uv,
                              const double* score, int32_t* ids_out, uint8_t* result, int32_t* fail_view, float* sim_out) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || !mp || n < 0) return MSCKF_ERR_ARG;
     if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
     if (n == 0) return MSCKF_NOOP;                                   // MSCKF.py:286
@@ -3886,6 +3933,7 @@ int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t
 }
 
 int msckf_tracks_descriptor(msckf_ctx* c, int32_t id, float* row, int32_t* M_out, float* views) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c) return MSCKF_ERR_ARG;
     const int at = c->mirror.row_of(id);
     if (at < 0) return MSCKF_ERR_ARG;
@@ -3904,6 +3952,7 @@ int msckf_tracks_descriptor(msckf_ctx* c, int32_t id, float* row, int32_t* M_out
 }
 
 int msckf_tracks_load_where(msckf_ctx* c, int32_t n_slots, const int32_t* slots, int32_t* F_out, int32_t* ids_out, int32_t cap) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || n_slots < 0 || cap < 0 || !F_out || (n_slots > 0 && !slots) || (cap > 0 && !ids_out)) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     std::vector<char> want(std::max(c->N, 1), n_slots == 0);
@@ -3929,6 +3978,7 @@ int msckf_tracks_load_where(msckf_ctx* c, int32_t n_slots, const int32_t* slots,
 }
 
 int msckf_tracks_counters(msckf_ctx* c, int32_t n, const int32_t* ids, int32_t* lost_for, int32_t* tracked_for) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || n < 0 || (n > 0 && !ids)) return MSCKF_ERR_ARG;
     for (int i = 0; i < n; ++i) if (c->mirror.row_of(ids[i]) < 0) return MSCKF_ERR_ARG;
     for (int i = 0; i < n; ++i) {
@@ -3940,6 +3990,7 @@ int msckf_tracks_counters(msckf_ctx* c, int32_t n, const int32_t* ids, int32_t* 
 }
 
 int msckf_tracks_clone_views(msckf_ctx* c, int32_t* views) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || (c->N > 0 && !views)) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     for (int s = 0; s < c->N; ++s) views[s] = 0;
@@ -3952,6 +4003,7 @@ int msckf_tracks_clone_views(msckf_ctx* c, int32_t* views) {
 
 int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, double* uv, double* dir, double* conf,
                      double* line_base, double* idp_base, double* idp_m, double* idp_rho, int32_t* anchor_slot) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c) return MSCKF_ERR_ARG;
     const int row = c->mirror.row_of(id);
     if (row < 0) return MSCKF_ERR_ARG;
@@ -3990,6 +4042,7 @@ int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, d
 }
 
 int msckf_tracks_count(msckf_ctx* c, int32_t* n_tracks, int32_t* n_views) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c) return MSCKF_ERR_ARG;
     if (n_tracks) *n_tracks = (int32_t)c->mirror.n_tracks();
     if (n_views) *n_views = (int32_t)c->mirror.n_views();
@@ -3997,6 +4050,7 @@ int msckf_tracks_count(msckf_ctx* c, int32_t* n_tracks, int32_t* n_views) {
 }
 
 int msckf_tracks_dropped(msckf_ctx* c, int32_t* ids, int32_t cap) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || cap < 0 || (cap > 0 && !ids)) return MSCKF_ERR_ARG;
     const int n = (int)c->mirror.dropped().size();
     if (n > 0 && cap > 0) std::memcpy(ids, c->mirror.dropped().data(), (size_t)std::min(n, (int)cap) * 4);
@@ -4007,6 +4061,7 @@ size_t msckf_block_doubles(const msckf_ctx* c) { return c ? (size_t)c->dc * (c->
 
 int msckf_export_block(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accepted) {
     if (!c || !dst) return MSCKF_ERR_ARG;
+    if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
     if (!c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = msckf_block_doubles(c) * 8;
@@ -4055,6 +4110,7 @@ int begin_merge(msckf_ctx* c) {
 int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int device_ptr,
                          int32_t total_accepted) {
     if (!c || !blocks || n_blocks < 1) return MSCKF_ERR_ARG;
+    if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
     if (!c->have_state) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const int dc = c->dc;
@@ -4110,6 +4166,7 @@ int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int
 // ---- group exchange: the sharded band pipeline --------------------------------------
 int msckf_set_group_exchange(msckf_ctx* c, int on) {
     if (!c) return MSCKF_ERR_ARG;
+    if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
     c->xchg = on != 0;
     c->have_features = false;             // the next msckf_set_features plans with the new layout
     c->plan_valid = false;
@@ -4214,6 +4271,7 @@ int msckf_exchange_split_rule(const msckf_ctx* c, int32_t N, int32_t F, const in
 
 int msckf_export_groups(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accepted) {
     if (!c || !dst) return MSCKF_ERR_ARG;
+    if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
     if (!c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = msckf_group_record_doubles(c) * 8;
@@ -4266,6 +4324,7 @@ int collect_masks(msckf_ctx* c, const double* recs, long long rec_stride, int n_
 
 int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int device_ptr, int32_t total_accepted, const uint8_t* flags) {
     if (!c || !records || n_rec < 1) return MSCKF_ERR_ARG;
+    if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
     if (!c->have_state) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->N, dc = c->dc;

@@ -207,6 +207,44 @@ int msckf_update_sigma(msckf_ctx* ctx, int32_t N, const double* P,
  * an entry that is not finite or not > 0. */
 int msckf_set_view_sigma(msckf_ctx* ctx, const double* sigma_view);
 
+/* ---- robust per-view weights (NOT in the reference) --------------------- *
+ * The reference's only defence against a bad observation is the gate (MSCKF.py:562-579), all or nothing per
+ * track: one mismatched keypoint costs every good view of its track.  With a loss set here, every call that
+ * runs K1 (msckf_update, msckf_update_sigma, msckf_run, msckf_run_timed, msckf_run_compress, the retry inside
+ * msckf_get_result) first reweights each view once at the linearisation point -- iteratively reweighted least
+ * squares with the one iteration an EKF step has -- from the batch's inverse-depth points as they stand (behind
+ * msckf_run_select and its refinement), the resident clone poses and K^-1, in fp64 in both dtypes:
+ *   e_v     the view's two residual components as K1 forms them (z / z_w - p_xy / p_z, normalised image coordinates)
+ *   b_v     the base weight: sigma / sigma_v where per-view noise is in force (above), else 1
+ *   s_v   = b_v |e_v|_2 / sigma                       the whitened residual norm
+ *   omega   Huber: min(1, k / s)      Cauchy: 1 / (1 + (s / k)^2)
+ *   phi_v = max(sqrt(omega(s_v)), w_min)              exactly 1 under Huber up to s_v == k, and 1 where s_v is not finite
+ *   w_v   = b_v phi_v                                 what K1 multiplies the view's rows of r, H_x and H_f by
+ * A track the run skips (msckf_run_select: no MSCKF_SEL_VALID) keeps w_v = b_v and reports s_v = 0.  Everything
+ * behind K1 is the code that runs without the option, and the gate's degrees of freedom stay 2M - rank.  The
+ * weights of a run live in an array of their own: the base weights are never overwritten, so repeated runs of
+ * one batch form the same weights and never compound them.
+ *
+ * msckf_set_robust: a setting of the context.  Off after msckf_create; it survives msckf_set_state and batch
+ * loads; NULL or loss 0 turns it off, and with it off the engine launches and computes exactly what it did
+ * before the option existed.  MSCKF_ERR_ARG, with nothing changed: loss outside 0..2, reserved != 0, k not
+ * finite or not > 0, w_min outside (0, 1].  Typical: Huber k = 1.345, Cauchy k = 2.385, w_min = 0.05.
+ * msckf_get_view_weights: waits for the stream; w_v and s_v of the last run in the caller's view order (sumM
+ * each, the order of obs_uv; any pointer may be NULL) and n_down, the number of views with phi_v < 1.
+ * MSCKF_ERR_STATE when the loaded batch's last run did not have the option on, or its results have been voided
+ * since (whatever voids msckf_get_result: a new batch, msckf_set_state, propagation, clone bookkeeping). */
+#define MSCKF_ROBUST_OFF 0
+#define MSCKF_ROBUST_HUBER 1
+#define MSCKF_ROBUST_CAUCHY 2
+typedef struct msckf_robust_params {
+    int32_t loss;        /* MSCKF_ROBUST_* */
+    int32_t reserved;    /* 0 */
+    double k;            /* the loss's scale, in whitened units (sigmas) */
+    double w_min;        /* floor of phi, in (0, 1] */
+} msckf_robust_params;
+int msckf_set_robust(msckf_ctx* ctx, const msckf_robust_params* params);
+int msckf_get_view_weights(msckf_ctx* ctx, double* w, double* s, int32_t* n_down);
+
 /* ---- resident path: the same update split so inputs can stay in HBM ---- */
 /* Upload filter state read by update(): P, clone poses, gravity, K^-1, sigma, chi2 table. */
 int msckf_set_state(msckf_ctx* ctx, int32_t N, const double* P,

@@ -45,7 +45,14 @@ SYMBOLS = [
     "msckf_tracks_match", "msckf_tracks_match_frame", "msckf_tracks_descriptor",
     "msckf_update_sigma", "msckf_set_view_sigma",
     "msckf_run_rows", "msckf_run_fix", "msckf_get_rows_gate",
+    "msckf_set_robust", "msckf_get_view_weights",
 ]
+ROBUST_OFF, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2
+
+
+class RobustParamsC(C.Structure):
+    """msckf_robust_params: the loss in front of K1, its scale in whitened units and the floor of the weight factor."""
+    _fields_ = [("loss", C.c_int32), ("reserved", C.c_int32), ("k", C.c_double), ("w_min", C.c_double)]
 
 
 class Config(C.Structure):
@@ -140,6 +147,10 @@ def load():
     lib.msckf_update_sigma.restype = C.c_int
     lib.msckf_set_view_sigma.argtypes = [vp, _dp]
     lib.msckf_set_view_sigma.restype = C.c_int
+    lib.msckf_set_robust.argtypes = [vp, C.POINTER(RobustParamsC)]
+    lib.msckf_set_robust.restype = C.c_int
+    lib.msckf_get_view_weights.argtypes = [vp, _dp, _dp, _ip]
+    lib.msckf_get_view_weights.restype = C.c_int
     lib.msckf_set_state.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, C.c_int32]
     lib.msckf_set_state.restype = C.c_int
     lib.msckf_set_features.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp]

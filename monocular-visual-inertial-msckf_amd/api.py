@@ -241,6 +241,42 @@ class UpdateEngine:
             raise ValueError(f"view_sigma holds {vs.size} entries, the loaded batch {n} views")
         self._check(self._lib.msckf_set_view_sigma(self._h, _ffi.dptr(vs)), allow_noop=False)
 
+    _ROBUST_LOSSES = {"huber": _ffi.ROBUST_HUBER, "cauchy": _ffi.ROBUST_CAUCHY}
+
+    def set_robust(self, loss=None, k: float = 1.345, w_min: float = 0.05):
+        """A robust loss on the reprojection residual in front of K1 (`msckf_set_robust`; not in the reference): every
+        view is reweighted once at the linearisation point, `w_v = b_v max(sqrt(omega(s_v)), w_min)` with
+        `s_v = b_v |e_v| / sigma` the whitened residual norm and `b_v` the base weight of `set_view_sigma` (else 1).
+        `loss`: None (off), "huber" (`omega = min(1, k / s)`, typical k 1.345) or "cauchy" (`1 / (1 + (s / k)^2)`,
+        typical k 2.385); a number is passed on as the C constant.  A setting of the engine: it survives `set_state`
+        and batch loads, and every call that runs the update honours it, the one-shot and the reference-shaped ones
+        included.  `EngineError` (`ERR_ARG`) for an unknown loss, k not finite or not > 0, w_min outside (0, 1]; the
+        setting then stays as it was."""
+        if loss is None:
+            self._check(self._lib.msckf_set_robust(self._h, None), allow_noop=False)
+            return
+        if isinstance(loss, str):
+            if loss not in self._ROBUST_LOSSES:
+                raise ValueError("loss must be None, 'huber' or 'cauchy'")
+            loss = self._ROBUST_LOSSES[loss]
+        rp = _ffi.RobustParamsC(int(loss), 0, float(k), float(w_min))
+        self._check(self._lib.msckf_set_robust(self._h, C.byref(rp)), allow_noop=False)
+
+    def view_weights(self) -> dict:
+        """`w` and `s` per view of the last run under `set_robust`, in the input order of the views, and `n_down`, the
+        number of views whose factor `phi_v` was below 1 (`msckf_get_view_weights`; waits for the stream).  A track
+        the run skipped reports `w = b`, `s = 0`.  `EngineError` (`ERR_STATE`) when the loaded batch's last run did not
+        have the option on or its results were voided since."""
+        n = getattr(self, "_views", None)
+        # (a batch of the track store: the engine counts its views; w is finite for every view there is)
+        cap = n if n is not None else max(self._F, 1) * self.max_track
+        w, s = np.full(max(cap, 1), np.nan), np.full(max(cap, 1), np.nan)
+        nd = np.zeros(1, dtype=np.int32)
+        self._check(self._lib.msckf_get_view_weights(self._h, _ffi.dptr(w), _ffi.dptr(s), _ffi.iptr(nd)), allow_noop=False)
+        if n is None:
+            n = int(np.count_nonzero(~np.isnan(w)))
+        return {"w": w[:n].copy(), "s": s[:n].copy(), "n_down": int(nd[0])}
+
     def run(self):
         self._check(self._lib.msckf_run(self._h), allow_noop=False)
         self._rows_run = False
@@ -999,6 +1035,7 @@ class UpdateEngine:
         `view_sigma`: optional mapping feature key -> one standard deviation per view, in the order of
         `Feature.keypoints` and in `sigma_image`'s units (R_o = blockdiag(sigma_v^2 I_2) in place of `:589`; a
         feature the mapping does not name stays at `sigma_image`).  `None`: the reference's update.
+        A robust loss needs no argument here: `set_robust` is a setting of the engine and this call honours it.
         Returns the status (0 updated / 1 no-op); mutates `filt` like the reference."""
         from .pack import problem_from_reference, view_sigma_from_reference
         from .inject import inject_state
@@ -1021,6 +1058,7 @@ class UpdateEngine:
         `view_sigma`: as in `update`, keyed like `filt.features`.
         `refine_iters`: 0 the reference's linear triangulation; 1..32 refines each triangulated point on the device
         under the current clone poses before the update (`run_select`); the features then carry the refined points.
+        A robust loss set with `set_robust` stays in force (no argument here): its weights are formed at the refreshed points.
         Returns 0 updated / 1 no-op."""
         import dataclasses
         from .pack import problem_from_reference, select_params_from_reference, tracks_from_reference, view_sigma_from_reference
@@ -1058,7 +1096,8 @@ class UpdateEngine:
     def prune_poorest_camera_states(self, filt, refine_iters: int = 0) -> int:
         """Drop-in for `MSCKF.prune_poorest_camera_states()` (reference `MSCKF.py:710-737`): the two clones seen by
         the fewest features, the features seen by them -> `get_valid_features` -> `update` -> `remove_cameras`,
-        composed on the resident engine (`_prune`).  `refine_iters` as in `process_features`.  Returns 0 updated / 1 no update."""
+        composed on the resident engine (`_prune`).  `refine_iters` as in `process_features`; `set_robust`, a setting of the
+        engine, is honoured without an argument.  Returns 0 updated / 1 no update."""
         count = {}
         for ft in filt.features.values():                                             # :712-716
             for ci in ft.camera_indices:
@@ -1070,8 +1109,8 @@ class UpdateEngine:
         """Drop-in for `MSCKF.prune_camera_states()` (reference `MSCKF.py:663-680`): every
         `int(max_number_of_camera_states / camera_states_to_delete)`-th clone of the window (position i > 0 with
         i % step == 0, `:665-667`), the features seen by them -> `get_valid_features` -> `update` ->
-        `remove_cameras`, composed on the resident engine (`_prune`).  `refine_iters` as in `process_features`.
-        Returns 0 updated / 1 no update."""
+        `remove_cameras`, composed on the resident engine (`_prune`).  `refine_iters` as in `process_features`; `set_robust`,
+        a setting of the engine, is honoured without an argument.  Returns 0 updated / 1 no update."""
         step = int(filt.max_number_of_camera_states / filt.camera_states_to_delete)   # :666
         drop = {k: cam for i, (k, cam) in enumerate(filt.state.cameras.items()) if i > 0 and i % step == 0}
         return self._prune(filt, drop, refine_iters)

@@ -42,10 +42,12 @@
 #include "k_tracks.h"
 #include "k_match.h"
 #include "k_rows.h"
+#include "k_robust.h"
 #include "run_outcome.h"
 #include "track_mirror.h"
 #include "batch_order.h"
 #include "rows_args.h"
+#include "robust_weight.h"
 
 static_assert(TrackMirror::kOk == MSCKF_OK && TrackMirror::kErrArg == MSCKF_ERR_ARG && TrackMirror::kErrDupSlot == MSCKF_ERR_DUP_SLOT,
               "track_mirror.h returns the ABI's codes");
@@ -287,7 +289,8 @@ struct RunRecord {
     bool fused_leaves = false;            // pipeline: ... and the leaves with them (k_leaf_root_gain)
     int rows_m = 0;                       // rows: the measurement's row count (msckf_stats.stacked_rows)
     bool injected = false;                // msckf_commit_inject added this run's dx to the nominal state: a run is injected once
-    long serial = 0;                      // finish_run numbers the runs
+    bool robust = false;                  // pipeline: K1 read the robust weights k_robust wrote for it (msckf_get_view_weights)
+    long serial = 0;                     // finish_run numbers the runs
 };
 
 }  // namespace
@@ -414,6 +417,14 @@ struct msckf_ctx {
     bool have_w = false;
     size_t w_raw_off = 0;
     Buf dObsW;
+    // robust per-view weights (msckf_set_robust, k_robust.h): a setting of the context, loss 0 = off.  With it on, every K1 launch
+    // is preceded by k_robust, which writes w_v = b_v phi(s_v) | s_v (sorted view order, sumM doubles each) into dRob -- K1 reads
+    // obs_w from there; dObsW, the base weights b_v, is only read.  rob_k1: the K1 in the stream for the current batch did so;
+    // rob_launched: the parameters of that launch (n_down of msckf_get_view_weights)
+    msckf_robust_params robust{};
+    msckf_robust_params rob_launched{};
+    Buf dRob;
+    bool rob_k1 = false;
     const GatherRec* gather_rec = nullptr; // the batch's records where k_gather read them (pinned host image or the raw arena)
     std::vector<double> chi2_cache;
     bool defer_state_sync = false;        // msckf_update: the feature upload's sync covers the state upload
@@ -1366,7 +1377,34 @@ inline double* rem_rows(msckf_ctx* c) { return rem_in_record(c) ? ptr<double>(c-
 inline int* drem_count(msckf_ctx* c) { return reinterpret_cast<int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1)); }   // behind the matrix
 inline int* rem_count(msckf_ctx* c) { return rem_in_record(c) ? reinterpret_cast<int*>(ptr<double>(c->dRbuf) + rec_rem_off(c)) : drem_count(c); }
 
+// msckf_set_robust is on: k_robust in front of K1, on the main stream and in front of the fork to the second stream, so that
+// every K1 of the launch set below (short, split, wide) reads what it wrote.  The weights go to dRob; a.obs_w is pointed at them.
+int launch_robust(msckf_ctx* c, FeatureArgs& a) {
+    const int sumM = c->sumM;
+    if (c->dRob.bytes < (size_t)2 * sumM * 8) {          // (grows with the largest batch; a run nobody waited for may still read the old one)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream2));
+        if (int rc = ensure(c, c->dRob, (size_t)2 * sumM * 8)) return rc;
+    }
+    RobustArgs r{};
+    r.F = c->F; r.sumM = sumM;
+    r.view_ptr = a.view_ptr; r.obs_uv = a.obs_uv; r.obs_slot = a.obs_slot; r.obs_b = a.obs_w;
+    r.idp_base = a.idp_base; r.idp_m = a.idp_m; r.idp_rho = a.idp_rho; r.cam_R = a.cam_R; r.cam_t = a.cam_t;
+    r.select = a.select;
+    for (int i = 0; i < 9; ++i) r.Kinv[i] = c->Kinv[i];
+    r.sigma = c->sigma;
+    r.loss = c->robust.loss; r.k = c->robust.k; r.w_min = c->robust.w_min;
+    r.w = ptr<double>(c->dRob); r.s = r.w + sumM;
+    hipLaunchKernelGGL(k_robust, dim3((sumM + ROBUST_THREADS - 1) / ROBUST_THREADS), dim3(ROBUST_THREADS), 0, c->stream, r);
+    HIPCHK(c, hipGetLastError());
+    a.obs_w = r.w;
+    c->rob_launched = c->robust;
+    c->rob_k1 = true;
+    return MSCKF_OK;
+}
+
 int launch_feature(msckf_ctx* c) {
+    c->rob_k1 = false;
     if (c->F == 0) return MSCKF_OK;
     FeatureArgs a{};
     a.F = c->F; a.ldp = c->d;
@@ -1384,7 +1422,8 @@ int launch_feature(msckf_ctx* c) {
     a.select = c->use_select ? ptr<unsigned char>(c->dSelFlags) : nullptr;
     a.stamps = c->dStamps.p ? ptr<long long>(c->dStamps) + 8 * 8192 : nullptr;   // behind the fold stamps
     a.zero_idx = c->ord.stack_elems;
-    c->gate_direct = c->want_direct && !c->use_select;      // (long tracks: k_feature<64, true> mirrors its track's results as well)
+    if (c->robust.loss != MSCKF_ROBUST_OFF) { if (int rcr = launch_robust(c, a)) return rcr; }
+    c->gate_direct =c->want_direct && !c->use_select;      // (long tracks: k_feature<64, true> mirrors its track's results as well)
     if (c->gate_direct) { a.rank_h = static_cast<int*>(c->hGate); a.acc_h = static_cast<unsigned char*>(c->hGate) + (size_t)c->ord.Fs * 4; }
     // one launch per class of tracks: the short tracks [0, Fb) and the long ones [Fb, F), which are split (k_feature<64, true>
     // writes their narrow and remainder blocks)
@@ -2031,6 +2070,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     if (c->state_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_state, 0)); c->state_pending = false; }
     if (!c->feature_launched && (rc = launch_feature(c)) != MSCKF_OK) return rc;
     c->feature_launched = false;
+    rec.robust = c->F > 0 && c->rob_k1;
     if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[1], c->stream));
     // split long tracks: their remainder blocks' tree follows k_feature<64, true> on the second stream, beside the band
     // pipeline; the leaves below read the narrow blocks that kernel wrote
@@ -2478,7 +2518,7 @@ void msckf_destroy(msckf_ctx* c) {
                   &c->dFlush, &c->dFlushOff, &c->dFeatInfo, &c->dCommBuf, &c->dAssocUV, &c->dAssocRes,
                   &c->dGsEx, &c->dGsFlag, &c->dGsProg, &c->dMProg, &c->dMFlush, &c->dRootFlush, &c->dXRootFlush,
                   &c->dSplit, &c->dRem, &c->dNom, &c->dTrk, &c->dTrkRows, &c->dTrkRowSorted,
-                  &c->dDescViews, &c->dDescRow, &c->dMatch, &c->dRows};
+                  &c->dDescViews, &c->dDescRow, &c->dMatch, &c->dRows, &c->dRob};
     for (Buf* b : all) if (b->p && !b->view) (void)hipFree(b->p);
     for (Buf* b : {&c->dPoseArena, &c->dFeatArena, &c->dRawArena, &c->dResArena, &c->dGateArena, &c->dPlanArena}) if (b->p) (void)hipFree(b->p);
     for (void* h : {c->hPose, c->hFeat, c->hRes, c->hGate, c->hP}) if (h) (void)hipHostFree(h);
@@ -2873,6 +2913,37 @@ int msckf_set_view_sigma(msckf_ctx* c, const double* sigma_view) {
     if (int rcw = launch_gather_w(c)) return rcw;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_w = true;
+    return MSCKF_OK;
+}
+
+int msckf_set_robust(msckf_ctx* c, const msckf_robust_params* p) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!p) { c->robust = msckf_robust_params{}; return MSCKF_OK; }
+    if (!robust_params_ok(p->loss, p->reserved, p->k, p->w_min)) return MSCKF_ERR_ARG;        // (nothing changed)
+    c->robust = *p;
+    return MSCKF_OK;
+}
+
+int msckf_get_view_weights(msckf_ctx* c, double* w, double* s, int32_t* n_down) {
+    if (!c) return MSCKF_ERR_ARG;
+    // the loaded batch's last run, with the option on, its results not voided since (RunRecord::ran)
+    if (!c->have_state || !c->have_features || !c->ord.valid || !c->last.ran || !c->last.robust) return MSCKF_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int F = c->F, sumM = c->sumM;
+    std::vector<double> sorted((size_t)2 * sumM);
+    HIPCHK(c, hipMemcpy(sorted.data(), c->dRob.p, sorted.size() * 8, hipMemcpyDeviceToHost));
+    const double *ws = sorted.data(), *ss = ws + sumM;
+    const msckf_robust_params& rp = c->rob_launched;
+    int down = 0;
+    for (int i = 0; i < sumM; ++i) down += robust_phi(rp.loss, rp.k, rp.w_min, ss[i]) < 1.0 ? 1 : 0;
+    // sorted position -> the caller's view order: track ord.perm[sidx] of the input, its views in the order it gave them
+    for (int sidx = 0; sidx < F; ++sidx) {
+        const int f = c->ord.perm[sidx], a = c->h_view_in[f], o = c->ord.h_view[sidx], M = c->ord.h_view[sidx + 1] - o;
+        if (w) std::memcpy(w + a, ws + o, (size_t)M * 8);
+        if (s) std::memcpy(s + a, ss + o, (size_t)M * 8);
+    }
+    if (n_down) *n_down = down;
     return MSCKF_OK;
 }
 

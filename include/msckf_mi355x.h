@@ -570,6 +570,46 @@ typedef struct msckf_match_params {
 int msckf_tracks_match_frame(msckf_ctx* ctx, const msckf_match_params* params, int32_t n, const float* desc /*n*D*/,
                              const double* uv /*2n*/, const double* score /*n*/, int32_t* ids_out /*n*/, uint8_t* result /*n*/,
                              int32_t* fail_view /*n, nullable*/, float* sim_out /*n, nullable*/);
+/* ---- the match's search window and distinctiveness margin (NOT in the reference; off by default) ---- *
+ * On repeated texture two tracks with near-equal descriptors break each other's mutuality or pair with each other's
+ * keypoints, and everything downstream can only discard the damage a view or a track at a time.  Two options of the
+ * context, both off after msckf_create: search_radius (pixels; 0 = off; +inf is legal) and min_margin (0 = off).
+ * THE RULE.  A, B, S = A B^T in fp32 as above.  allowed(i, j): the radius is off, or
+ * (u_j - u^_i)^2 + (v_j - v^_i)^2 <= radius^2, formed in double, where (u_j, v_j) is keypoint j of the frame and
+ * (u^_i, v^_i) the LAST stored keypoint of table track i: view count - 1 of its row as it stands in the store when the
+ * match runs (behind an append the appended keypoint; behind msckf_remove_clones the last view that survived).
+ * S'[i][j] = S[i][j] where allowed, else -inf.  m12[i] = argmax_j S'[i][.], lowest index among equals, or none when no j
+ * is allowed; s1 = that maximum; s2 = the largest S'[i][j] over j != m12[i], -inf when there is none.  The same per
+ * column: m21, c1, c2.  Each table element gets a reason code, the first that applies:
+ *   1  no keypoint inside the window
+ *   2  m21[m12[i]] != i (not mutual)
+ *   3  not s1 > min_cosine_similarity (strict; compared in double on the fp32 value, as without the options)
+ *   4  the margin is on and not (s1 - s2 > min_margin and c1 - c2 > min_margin), c1 / c2 those of column m12[i];
+ *      strict, in double on the fp32 values; a second best of -inf passes
+ *   0  the pair (i, m12[i])
+ * With radius = +inf and margin 0 the rule is the plain one.  Everything behind the pairs is unchanged: the numbering of
+ * the unmatched keypoints, msckf_tracks_frame's path, the counters, the descriptors and rows, and the return of 1 with
+ * nothing changed for a frame in which no pair survives.
+ * msckf_tracks_set_match_options: NULL turns both off; MSCKF_ERR_ARG, with nothing changed, for a negative or NaN value.
+ * The options are STICKY: a setting of the context, which msckf_tracks_reset and msckf_set_state do not clear.  With both
+ * off, msckf_tracks_match and msckf_tracks_match_frame launch exactly the kernels and form exactly the bits they did
+ * before the options existed; with either on they run k_match_last_uv (window only), k_match_argmax_opt twice and
+ * k_match_resolve_opt (k_match.h). */
+typedef struct msckf_match_options {
+    double search_radius;           /* pixels around the track's last keypoint; 0 = off                 */
+    double min_margin;              /* best minus second-best similarity, row and column; 0 = off       */
+} msckf_match_options;
+int msckf_tracks_set_match_options(msckf_ctx* ctx, const msckf_match_options* options);
+/* msckf_tracks_match with the frame's keypoints, uv[2 n]: the match-only probe under the window.  Its checks are those
+ * of msckf_tracks_match, and MSCKF_ERR_ARG for a non-finite keypoint.  msckf_tracks_match itself has no keypoints: it
+ * answers MSCKF_ERR_STATE while a radius is on; with a margin only, it applies the margin. */
+int msckf_tracks_match_at(msckf_ctx* ctx, double min_cosine_similarity, int32_t desc_dim, int32_t n, const float* desc /*n*D*/,
+                          const double* uv /*2n*/, int32_t* track_id_out /*n*/, float* sim_out /*n, nullable*/);
+/* The table of the last call that ran a match (msckf_tracks_match, _match_at, _match_frame with n > 0 on a store that
+ * holds tracks), in creation order: *T_out elements; the track id and the reason code of the first min(*T_out, cap) of
+ * them (ids_out, why_out: nullable when that is 0).  Without the options the codes are 0 / 2 / 3, derived on the host.
+ * Empty behind msckf_tracks_reset and msckf_set_state.  Blocking. */
+int msckf_tracks_match_report(msckf_ctx* ctx, int32_t* T_out, int32_t* ids_out, uint8_t* why_out, int32_t cap);
 /* One track's descriptors as they stand on the device (blocking; any output may be NULL): its match row, row[D], its M
  * views and their descriptors, views[M*D] (room for max_track * D).  MSCKF_ERR_ARG: unknown id; MSCKF_ERR_STATE: the
  * track has a view without a descriptor. */

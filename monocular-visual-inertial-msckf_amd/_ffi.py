@@ -43,6 +43,7 @@ SYMBOLS = [
     "msckf_tracks_count", "msckf_tracks_dropped",
     "msckf_tracks_frame", "msckf_tracks_load_where", "msckf_tracks_counters", "msckf_tracks_clone_views",
     "msckf_tracks_match", "msckf_tracks_match_frame", "msckf_tracks_descriptor",
+    "msckf_tracks_set_match_options", "msckf_tracks_match_at", "msckf_tracks_match_report",
     "msckf_update_sigma", "msckf_set_view_sigma",
     "msckf_run_rows", "msckf_run_fix", "msckf_get_rows_gate",
     "msckf_set_robust", "msckf_get_view_weights",
@@ -85,6 +86,11 @@ class MatchParamsC(C.Structure):
     """msckf_match_params: msckf_frame_params + the matcher's threshold, the descriptor dimension, the first new id."""
     _fields_ = [("K", C.c_double * 9), ("epipolar_threshold", C.c_double), ("homography_threshold", C.c_double),
                 ("min_cosine_similarity", C.c_double), ("desc_dim", C.c_int32), ("first_new_id", C.c_int32)]
+
+
+class MatchOptionsC(C.Structure):
+    """msckf_match_options: the match's search radius (pixels) and distinctiveness margin; 0 = off."""
+    _fields_ = [("search_radius", C.c_double), ("min_margin", C.c_double)]
 
 
 DESC_DIM = 64           # floats a stored descriptor row holds: desc_dim is 1..64
@@ -277,8 +283,11 @@ def load():
     lib.msckf_tracks_match.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, _fp, _ip, _fp]
     lib.msckf_tracks_match_frame.argtypes = [vp, C.POINTER(MatchParamsC), C.c_int32, _fp, _dp, _dp, _ip, _up, _ip, _fp]
     lib.msckf_tracks_descriptor.argtypes = [vp, C.c_int32, _fp, _ip, _fp]
+    lib.msckf_tracks_set_match_options.argtypes = [vp, C.POINTER(MatchOptionsC)]
+    lib.msckf_tracks_match_at.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, _fp, _dp, _ip, _fp]
+    lib.msckf_tracks_match_report.argtypes = [vp, _ip, _ip, _up, C.c_int32]
     for name in ("reset", "observe", "remove", "load", "get", "count", "dropped", "frame", "load_where", "counters", "clone_views",
-                 "match", "match_frame", "descriptor"):
+                 "match", "match_frame", "descriptor", "set_match_options", "match_at", "match_report"):
         getattr(lib, "msckf_tracks_" + name).restype = C.c_int
     lib.msckf_debug_split.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.msckf_debug_split.restype = C.c_int

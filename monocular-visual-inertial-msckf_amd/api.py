@@ -642,16 +642,51 @@ class UpdateEngine:
             raise ValueError("descriptors are (n, D)")
         return d
 
-    def tracks_match(self, descriptors, min_cosine_similarity: float = 0.82):
+    def set_match_options(self, search_radius=None, min_margin=None):
+        """The match's two defences against repeated texture (`msckf_tracks_set_match_options`; not in the reference, off
+        by default).  `search_radius` (pixels; None or 0: off; `inf` is legal): a track only meets the keypoints within
+        that distance of its last stored keypoint.  `min_margin` (None or 0: off): a pair also needs its similarity to
+        beat the second best of its row and of its column by more than the margin.  The rule in full stands in
+        `include/msckf_mi355x.h`.  A setting of the engine: `tracks_reset` and `set_state` leave it alone.
+        `EngineError` (`ERR_ARG`) for a negative or NaN value; the setting then stays as it was."""
+        if search_radius is None and min_margin is None:
+            self._check(self._lib.msckf_tracks_set_match_options(self._h, None), allow_noop=False)
+            return
+        mo = _ffi.MatchOptionsC(float(search_radius or 0.0), float(min_margin or 0.0))
+        self._check(self._lib.msckf_tracks_set_match_options(self._h, C.byref(mo)), allow_noop=False)
+
+    def tracks_match(self, descriptors, min_cosine_similarity: float = 0.82, keypoints=None):
         """The mutual-nearest-neighbour match of a frame's descriptors against the store's rows (reference
-        `FeatureExtractor.match`, `FeatureExtractor.py:62-84`); the store is untouched.  Returns (track id (n,) int32, -1
-        where unmatched; similarity (n,) fp32, 0 where unmatched).  Blocking."""
+        `FeatureExtractor.match`, `FeatureExtractor.py:62-84`); the store is untouched.  With `keypoints` (n, 2) the
+        match runs under the search window of `set_match_options` (`msckf_tracks_match_at`); without them it raises
+        `EngineError` (`ERR_STATE`) while a radius is set.  Returns (track id (n,) int32, -1 where unmatched; similarity
+        (n,) fp32, 0 where unmatched).  Blocking."""
         d = self._desc(descriptors)
         n, D = d.shape
         ids, sim = np.full(max(n, 1), -1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.float32)
-        self._check(self._lib.msckf_tracks_match(self._h, float(min_cosine_similarity), int(D), int(n), _ffi.dptr(d),
-                                                 _ffi.iptr(ids), _ffi.dptr(sim)), allow_noop=False)
+        if keypoints is None:
+            rc = self._lib.msckf_tracks_match(self._h, float(min_cosine_similarity), int(D), int(n), _ffi.dptr(d),
+                                              _ffi.iptr(ids), _ffi.dptr(sim))
+        else:
+            u = _ffi.f64(keypoints).reshape(-1)
+            if u.size != 2 * n:
+                raise ValueError("keypoints are (n, 2)")
+            rc = self._lib.msckf_tracks_match_at(self._h, float(min_cosine_similarity), int(D), int(n), _ffi.dptr(d),
+                                                 _ffi.dptr(u), _ffi.iptr(ids), _ffi.dptr(sim))
+        self._check(rc, allow_noop=False)
         return ids[:n].copy(), sim[:n].copy()
+
+    def tracks_match_report(self):
+        """The table of the last match, in the order the tracks were created: (track id (T,) int32, reason code (T,)
+        uint8: 0 paired, 1 no keypoint inside the window, 2 not mutual, 3 below the threshold, 4 below the margin).
+        Empty after `tracks_reset` / `set_state`.  Blocking."""
+        T = C.c_int32(0)
+        self._check(self._lib.msckf_tracks_match_report(self._h, C.addressof(T), None, None, 0), allow_noop=False)
+        cap = max(int(T.value), 1)
+        ids, why = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.uint8)
+        self._check(self._lib.msckf_tracks_match_report(self._h, C.addressof(T), _ffi.iptr(ids), _ffi.uptr(why), cap),
+                    allow_noop=False)
+        return ids[:int(T.value)].copy(), why[:int(T.value)].copy()
 
     def tracks_match_frame(self, keypoints, descriptors, scores, K, first_new_id: int, min_cosine_similarity: float = 0.82,
                            epipolar_threshold: float = 5.0, homography_threshold: float = 5.0):

@@ -528,6 +528,20 @@ struct msckf_ctx {
     bool desc_ready = false;
     int desc_D = 0;                       // the store's descriptor dimension; 0: not set yet
     PinStage trk_match_stage, trk_desc_stage;
+    // the matcher's options (msckf_tracks_set_match_options): a setting of the context, both 0 = off; tracks_clear leaves them
+    msckf_match_options match_opt{};
+    // the last match's table (msckf_tracks_match_report): the ids at the time of the match; the reason codes of the
+    // options' path come back with the pairs, those of the plain path are derived on demand from m12 / m21, which stay
+    // in dMatch until the next match (the plain path itself copies nothing more than it did).
+    struct MatchReport {
+        std::vector<int32_t> ids;
+        std::vector<uint8_t> why;
+        std::vector<float> sim;
+        bool derived = true;              // why[] is filled
+        size_t o_m12 = 0, o_m21 = 0;      // (plain path) where m12[T] and m21[n] stand in dMatch
+        int n = 0;
+        double min_cos = 0.0;
+    } match_rep;
     // direct measurement rows (k_rows.h): H | r | R go up as one pinned image; Y and the slabs' partial S live behind them
     Buf dRows;
     PinStage rows_stage;
@@ -2203,6 +2217,7 @@ void tracks_clear(msckf_ctx* c) {
     c->mirror.clear();
     c->batch_from_store = false;
     c->desc_D = 0;
+    c->match_rep = msckf_ctx::MatchReport{};      // (the matcher's options are the context's: they stay)
 }
 
 // capacity max_features tracks x max_track views, allocated on first use
@@ -3921,22 +3936,158 @@ static int match_run(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const f
     HIPCHK(c, hipStreamSynchronize(c->stream));
     pair.assign(reinterpret_cast<int*>(img + o_pair), reinterpret_cast<int*>(img + o_pair) + T);
     sim.assign(reinterpret_cast<float*>(img + o_sim), reinterpret_cast<float*>(img + o_sim) + T);
+    // what msckf_tracks_match_report needs to derive the codes 0 / 2 / 3 should it be asked
+    msckf_ctx::MatchReport& rep = c->match_rep;
+    rep.ids.resize(T);
+    for (size_t t = 0; t < T; ++t) rep.ids[t] = c->mirror.id(rows[t]);
+    rep.sim = sim;
+    rep.why.clear();
+    rep.derived = false;
+    rep.o_m12 = o_rows + T * 4; rep.o_m21 = o_rows + 3 * T * 4; rep.n = n; rep.min_cos = min_cos;
     return MSCKF_OK;
 }
 
-int msckf_tracks_match(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, int32_t* track_id_out, float* sim_out) {
+inline bool match_options_on(const msckf_ctx* c) { return c->match_opt.search_radius > 0.0 || c->match_opt.min_margin > 0.0; }
+
+// match_run with the options on (k_match.h: k_match_last_uv, k_match_argmax_opt twice, k_match_resolve_opt).  uv[2 n]: the
+// frame's keypoints; null only where the window is off.  The reason codes come back with the pairs.
+static int match_run_opt(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, const double* uv,
+                         const std::vector<int>& rows, std::vector<int>& pair, std::vector<float>& sim) {
+    const size_t T = rows.size(), nf = (size_t)n * DESC_DIM;
+    const bool window = c->match_opt.search_radius > 0.0;
+    // pinned image: frame | rows | frame keypoints | pair | sim | why
+    // device:       frame | rows | frame keypoints | table keypoints | m12 | s1 | s2 | m21 | c1 | c2
+    const size_t o_rows = nf * 4, o_uvb = (o_rows + T * 4 + 7) / 8 * 8, o_up = o_uvb + (size_t)n * 16;
+    const size_t o_pair = o_up, o_sim = o_pair + T * 4, o_why = o_sim + T * 4;
+    const size_t o_uva = o_up, o_m12 = o_uva + T * 16, o_s1 = o_m12 + T * 4, o_s2 = o_s1 + T * 4, o_m21 = o_s2 + T * 4;
+    const size_t o_c1 = o_m21 + (size_t)n * 4, o_c2 = o_c1 + (size_t)n * 4;
+    if (int rc = stage_acquire(c, c->trk_match_stage, o_why + T * 4)) return rc;
+    if (int rc = ensure(c, c->dMatch, o_c2 + (size_t)n * 4)) return rc;
+    char* img = static_cast<char*>(c->trk_match_stage.p);
+    float* hf = reinterpret_cast<float*>(img);
+    std::memset(hf, 0, nf * 4);
+    for (int i = 0; i < n; ++i) std::memcpy(hf + (size_t)i * DESC_DIM, desc + (size_t)i * D, (size_t)D * 4);
+    if (T) std::memcpy(img + o_rows, rows.data(), T * 4);
+    if (window) std::memcpy(img + o_uvb, uv, (size_t)n * 16);
+    else std::memset(img + o_uvb, 0, (size_t)n * 16);
+    char* dev = static_cast<char*>(c->dMatch.p);
+    HIPCHK(c, hipMemcpyAsync(dev, img, o_up, hipMemcpyHostToDevice, c->stream));
+    if (T) {
+        const float* dframe = reinterpret_cast<const float*>(dev);
+        const int* drows = reinterpret_cast<const int*>(dev + o_rows);
+        const double* uvb = reinterpret_cast<const double*>(dev + o_uvb);
+        double* uva = reinterpret_cast<double*>(dev + o_uva);
+        int* m12 = reinterpret_cast<int*>(dev + o_m12);
+        float* s1 = reinterpret_cast<float*>(dev + o_s1);
+        float* s2 = reinterpret_cast<float*>(dev + o_s2);
+        int* m21 = reinterpret_cast<int*>(dev + o_m21);
+        float* c1 = reinterpret_cast<float*>(dev + o_c1);
+        float* c2 = reinterpret_cast<float*>(dev + o_c2);
+        const double r = c->match_opt.search_radius;
+        if (window) hipLaunchKernelGGL(k_match_last_uv, dim3(((int)T + 255) / 256), dim3(256), 0, c->stream, c->trk, drows, (int)T, uva);
+        MatchOptArgs a{c->desc.row, drows, (int)T, dframe, nullptr, n, uva, uvb, r * r, window ? 1 : 0, m12, s1, s2};
+        hipLaunchKernelGGL(k_match_argmax_opt, dim3((a.nx + 15) / 16), dim3(64), 0, c->stream, a);
+        MatchOptArgs b{dframe, nullptr, n, c->desc.row, drows, (int)T, uvb, uva, r * r, window ? 1 : 0, m21, c1, c2};
+        hipLaunchKernelGGL(k_match_argmax_opt, dim3((b.nx + 15) / 16), dim3(64), 0, c->stream, b);
+        hipLaunchKernelGGL(k_match_resolve_opt, dim3(((int)T + 255) / 256), dim3(256), 0, c->stream, (int)T, (const int*)m12,
+                           (const float*)s1, (const float*)s2, (const int*)m21, (const float*)c1, (const float*)c2, min_cos,
+                           c->match_opt.min_margin, reinterpret_cast<int*>(img + o_pair), reinterpret_cast<float*>(img + o_sim),
+                           reinterpret_cast<int*>(img + o_why));
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    pair.assign(reinterpret_cast<int*>(img + o_pair), reinterpret_cast<int*>(img + o_pair) + T);
+    sim.assign(reinterpret_cast<float*>(img + o_sim), reinterpret_cast<float*>(img + o_sim) + T);
+    msckf_ctx::MatchReport& rep = c->match_rep;
+    rep.ids.resize(T);
+    rep.why.resize(T);
+    const int* why = reinterpret_cast<const int*>(img + o_why);
+    for (size_t t = 0; t < T; ++t) { rep.ids[t] = c->mirror.id(rows[t]); rep.why[t] = (uint8_t)why[t]; }
+    rep.sim = sim;
+    rep.derived = true;
+    return MSCKF_OK;
+}
+
+// the match of a call: the plain kernels with both options off (exactly the launches there were before the options), the
+// options' kernels otherwise
+static int match_any(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, const double* uv,
+                     const std::vector<int>& rows, std::vector<int>& pair, std::vector<float>& sim) {
+    if (!match_options_on(c)) return match_run(c, min_cos, D, n, desc, rows, pair, sim);
+    return match_run_opt(c, min_cos, D, n, desc, uv, rows, pair, sim);
+}
+
+static bool uv_finite(const double* uv, int32_t n) {
+    for (int i = 0; i < 2 * n; ++i) if (!std::isfinite(uv[i])) return false;
+    return true;
+}
+
+// msckf_tracks_match (uv null: no keypoints, so no window) and msckf_tracks_match_at
+static int tracks_match_impl(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, const double* uv, bool with_uv,
+                             int32_t* track_id_out, float* sim_out) {
     if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
     if (!c || n < 0 || (n > 0 && !track_id_out)) return MSCKF_ERR_ARG;
+    if (with_uv && n > 0 && (!uv || !uv_finite(uv, n))) return MSCKF_ERR_ARG;
     if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
+    if (!with_uv && c->match_opt.search_radius > 0.0) {
+        c->last_error = "msckf_tracks_match has no keypoints and a search radius is set: use msckf_tracks_match_at";
+        return MSCKF_ERR_STATE;
+    }
     std::vector<int> rows, pair;
     std::vector<float> sim;
     if (int rc = match_check(c, D, n, desc, rows)) return rc;
     for (int j = 0; j < n; ++j) { track_id_out[j] = -1; if (sim_out) sim_out[j] = 0.f; }
     if (n == 0 || rows.empty()) return MSCKF_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = match_run(c, min_cos, D, n, desc, rows, pair, sim)) return rc;
+    if (int rc = match_any(c, min_cos, D, n, desc, uv, rows, pair, sim)) return rc;
     for (size_t t = 0; t < rows.size(); ++t)
         if (pair[t] >= 0) { track_id_out[pair[t]] = c->mirror.id(rows[t]); if (sim_out) sim_out[pair[t]] = sim[t]; }
+    return MSCKF_OK;
+}
+
+int msckf_tracks_match(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, int32_t* track_id_out, float* sim_out) {
+    return tracks_match_impl(c, min_cos, D, n, desc, nullptr, false, track_id_out, sim_out);
+}
+
+int msckf_tracks_match_at(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, const double* uv,
+                          int32_t* track_id_out, float* sim_out) {
+    return tracks_match_impl(c, min_cos, D, n, desc, uv, true, track_id_out, sim_out);
+}
+
+int msckf_tracks_set_match_options(msckf_ctx* c, const msckf_match_options* o) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (!c) return MSCKF_ERR_ARG;
+    if (!o) { c->match_opt = msckf_match_options{}; return MSCKF_OK; }
+    if (!(o->search_radius >= 0.0) || !(o->min_margin >= 0.0)) return MSCKF_ERR_ARG;       // negative or NaN: nothing changed
+    c->match_opt = *o;
+    return MSCKF_OK;
+}
+
+int msckf_tracks_match_report(msckf_ctx* c, int32_t* T_out, int32_t* ids_out, uint8_t* why_out, int32_t cap) {
+    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (!c || !T_out || cap < 0) return MSCKF_ERR_ARG;
+    msckf_ctx::MatchReport& rep = c->match_rep;
+    const size_t T = rep.ids.size();
+    if (!rep.derived) {
+        // the plain path: 2 where m21[m12[t]] != t, else 3 where not sim > min_cos, else 0 (a pair)
+        std::vector<int> m12(T), m21(std::max(rep.n, 1));
+        if (T) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            const char* dev = static_cast<const char*>(c->dMatch.p);
+            HIPCHK(c, hipMemcpy(m12.data(), dev + rep.o_m12, T * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(m21.data(), dev + rep.o_m21, (size_t)rep.n * 4, hipMemcpyDeviceToHost));
+        }
+        rep.why.resize(T);
+        for (size_t t = 0; t < T; ++t) {
+            const int j = m12[t];
+            rep.why[t] = (j < 0 || j >= rep.n || m21[j] != (int)t) ? 2 : !((double)rep.sim[t] > rep.min_cos) ? 3 : 0;
+        }
+        rep.derived = true;
+    }
+    *T_out = (int32_t)T;
+    const size_t m = std::min(T, (size_t)cap);
+    if (m > 0 && (!ids_out || !why_out)) return MSCKF_ERR_ARG;
+    for (size_t t = 0; t < m; ++t) { ids_out[t] = rep.ids[t]; why_out[t] = rep.why[t]; }
     return MSCKF_OK;
 }
 
@@ -3951,10 +4102,11 @@ int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t
     std::vector<int> rows, pair;
     std::vector<float> sim;
     if (int rc = match_check(c, D, n, desc, rows)) return rc;
+    if (c->match_opt.search_radius > 0.0 && !uv_finite(uv, n)) return MSCKF_ERR_ARG;     // (the window reads them before the intake's own check)
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = desc_ensure(c)) return rc;
     const bool empty = rows.empty();                                 // :291-311: everything is created, the rows are raw
-    if (int rc = match_run(c, mp->min_cosine_similarity, D, n, desc, rows, pair, sim)) return rc;
+    if (int rc = match_any(c, mp->min_cosine_similarity, D, n, desc, uv, rows, pair, sim)) return rc;
     std::vector<int32_t> ids(n, -1);
     std::vector<float> ksim(n, 0.f);
     int matched = 0;

@@ -9,7 +9,7 @@ Both drive the whole run (clones, removals, the prune) and time only the intake 
 calls, the stream drained before and after.  The first run of each route is a warm-up; the routes are interleaved; the
 figure is the median over frames of the per-frame medians over the runs.  A record, not a gate.
 
-    python tools/match_intake.py [--runs 9]"""
+    python tools/match_intake.py [--runs 9] [--radius inf] [--margin 0]"""
 import argparse
 import os
 import sys
@@ -84,6 +84,8 @@ def drive(fx, eng, route):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=9)
+    ap.add_argument("--radius", type=float, default=None, help="search_radius of set_match_options on the device route (inf is legal)")
+    ap.add_argument("--margin", type=float, default=None, help="min_margin of set_match_options on the device route")
     a = ap.parse_args()
     from msckf_amd.api import UpdateEngine
     fx = match_ref.Fixture()
@@ -92,6 +94,8 @@ def main():
         out.setdefault(route, [])
         for _ in range(a.runs + 1):
             with UpdateEngine(max_clones=16, max_features=512, max_track=32) as eng:
+                if route == "device" and (a.radius is not None or a.margin is not None):
+                    eng.set_match_options(a.radius, a.margin)           # (a finite radius changes the pairs, and with them the run)
                 t = drive(fx, eng, route)
             out[route].append(t)
         del out[route][-(a.runs + 1)]                                # each block's first run is a warm-up

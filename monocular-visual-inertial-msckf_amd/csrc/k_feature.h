@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wave_ops.h"
+#include "view_row.h"             // K1 of one view
 #include "feature_dpp_groups.h"
 #include "batch_order.h"          // SplitRec, SPLIT_MAXG, SPLIT_GSLOTS
 
@@ -217,6 +218,14 @@ template <int K, int KEND, typename Fn>
 __device__ __forceinline__ void feature_static_for(Fn&& fn) {
     if constexpr (K < KEND) { fn(FTag<K>{}); feature_static_for<K + 1, KEND>(fn); }
 }
+// A track's verdict: rank, gamma and the code of FeatureArgs::accepted, with the optional mirrors in pinned host memory
+__device__ __forceinline__ void feature_verdict(const FeatureArgs& p, int f, int rank, double gamma, unsigned char code) {
+    p.rank[f] = rank;
+    p.gamma[f] = gamma;
+    p.accepted[f] = code;
+    if (p.acc_h) { p.rank_h[f] = rank; p.acc_h[f] = code; }
+}
+
 // RMAX > 2 * max track length of the launch (rows of the gate matrix held per lane).
 // NWV > 1 (split form only): NWV wavefronts per track -- every wavefront runs K1 / K2 (cheap, all in registers), the view groups
 // (K4) and the gate's column chunks are dealt over the wavefronts, the partial gate matrices are summed through LDS and wavefront
@@ -260,8 +269,7 @@ __global__ __launch_bounds__(64 * NWV, NWV > 1 ? 1 : (RMAX <= 24 ? 3 : 2)) void 
     };
     if (p.select && !(p.select[f] & 1)) {      // not in valid_features (MSCKF.py:453-455): no rows, not a rejection
         if (lane == 0 && wfirst) {
-            p.rank[f] = 0; p.gamma[f] = 0.0; p.accepted[f] = 3;
-            if (p.acc_h) { p.rank_h[f] = 0; p.acc_h[f] = 3; }
+            feature_verdict(p, f, 0, 0.0, 3);
             if constexpr (SPLIT) {
                 const SplitRec& sr = p.split[blockIdx.x];
                 for (int g = 0; g < sr.ng; ++g) if (sr.child[g] >= 0) { p.rank[sr.child[g]] = 3; p.accepted[sr.child[g]] = 3; }
@@ -278,74 +286,14 @@ __global__ __launch_bounds__(64 * NWV, NWV > 1 ? 1 : (RMAX <= 24 ? 3 : 2)) void 
     if (lane < R2) {
         const int o = v0 + view;
         const int s = p.obs_slot[o];
-        if ((lane & 1) == 0 && wfirst) sSlot[view] = s;
         const double* R = p.cam_R + 9 * s;
         const double* t = p.cam_t + 3 * s;
-        const double* R0 = p.cam_R0 + 9 * s;
-        const double* t0 = p.cam_t0 + 3 * s;
-        const double rho = p.idp_rho[f];
-        const double wx = rho * (p.idp_base[3 * f + 0] - t[0]) + p.idp_m[3 * f + 0];
-        const double wy = rho * (p.idp_base[3 * f + 1] - t[1]) + p.idp_m[3 * f + 1];
-        const double wz = rho * (p.idp_base[3 * f + 2] - t[2]) + p.idp_m[3 * f + 2];
-        // Ci_f = R^T w   (MSCKF.py:516)
-        const double px = R[0] * wx + R[3] * wy + R[6] * wz;
-        const double py = R[1] * wx + R[4] * wy + R[7] * wz;
-        const double pz = R[2] * wx + R[5] * wy + R[8] * wz;
-        // W_f = R Ci_f + t (MSCKF.py:517)
-        const double Wx = R[0] * px + R[1] * py + R[2] * pz + t[0];
-        const double Wy = R[3] * px + R[4] * py + R[5] * pz + t[1];
-        const double Wz = R[6] * px + R[7] * py + R[8] * pz + t[2];
-        const double u = p.obs_uv[2 * o], v = p.obs_uv[2 * o + 1];
-        double wv = 1.0;
-        if (p.obs_w) wv = p.obs_w[o];           // (uniform; asked for here, used at the end of K1)
-        const double zx = p.Kinv[0] * u + p.Kinv[1] * v + p.Kinv[2];
-        const double zy = p.Kinv[3] * u + p.Kinv[4] * v + p.Kinv[5];
-        const double zw = p.Kinv[6] * u + p.Kinv[7] * v + p.Kinv[8];
-        // (one division each for 1 / pz, 1 / zw and 1 / den; the other quotients of Camera.py are products with them: an IEEE
-        //  division is ~15 instructions here, and ~1e-16 relative is what the products differ by)
-        const double ia = 1.0 / pz;
-        const double jb = -px * (ia * ia);
-        const double jc = -py * (ia * ia);
-        const double izw = 1.0 / zw;
-        // u = [R0^T g ; (W_f - t0) x g]   (MSCKF.py:528-530)
-        const double gx = p.g[0], gy = p.g[1], gz = p.g[2];
-        const double u0 = R0[0] * gx + R0[3] * gy + R0[6] * gz;
-        const double u1 = R0[1] * gx + R0[4] * gy + R0[7] * gz;
-        const double u2 = R0[2] * gx + R0[5] * gy + R0[8] * gz;
-        const double ex = Wx - t0[0], ey = Wy - t0[1], ez = Wz - t0[2];
-        const double u3 = ey * gz - ez * gy;
-        const double u4 = ez * gx - ex * gz;
-        const double u5 = ex * gy - ey * gx;
-        const double den = u0 * u0 + u1 * u1 + u2 * u2 + u3 * u3 + u4 * u4 + u5 * u5;
-        double J0, J1, J2;   // this lane's row of J (Camera.py:57-58)
-        if ((lane & 1) == 0) {
-            res = zx * izw - px * ia;
-            J0 = ia; J1 = 0.0; J2 = jb;
-            a0 = -jb * py; a1 = -ia * pz + jb * px; a2 = ia * py;          // J skew(Ci_f), row 0
-        } else {
-            res = zy * izw - py * ia;
-            J0 = 0.0; J1 = ia; J2 = jc;
-            a0 = ia * pz - jc * py; a1 = jc * px; a2 = -ia * px;           // row 1
-        }
-        // H_f = J R^T (this row);  H_x[:,3:] = -H_f   (Camera.py:62,66; MSCKF.py:536)
-        h0 = J0 * R[0] + J1 * R[1] + J2 * R[2];
-        h1 = J0 * R[3] + J1 * R[4] + J2 * R[5];
-        h2 = J0 * R[6] + J1 * R[7] + J2 * R[8];
-        a3 = -h0; a4 = -h1; a5 = -h2;
-        if (den > 1e-6) {      // observability-constrained projection (MSCKF.py:532-534)
-            const double au = a0 * u0 + a1 * u1 + a2 * u2 + a3 * u3 + a4 * u4 + a5 * u5;
-            const double aud = au * (1.0 / den);
-            a0 -= aud * u0; a1 -= aud * u1; a2 -= aud * u2;
-            a3 -= aud * u3; a4 -= aud * u4; a5 -= aud * u5;
-        }
-        // per-view noise: R_o = blockdiag(sigma_v^2 I_2) in whitened form -- the view's rows of r, H_x and H_f times
-        // w_v = sigma / sigma_v, ONCE and in front of everything that forms Z, V or the gate's E: the null space below is that of
-        // diag(w) H_f, so the projected noise is sigma^2 I again and nothing behind K1 knows of the weights
-        if (p.obs_w) {
-            res *= wv;
-            a0 *= wv; a1 *= wv; a2 *= wv; a3 *= wv; a4 *= wv; a5 *= wv;
-            h0 *= wv; h1 *= wv; h2 *= wv;
-        }
+        const ViewPoint vp = view_point(R, t, p.idp_base + 3 * f, p.idp_m + 3 * f, p.idp_rho[f], p.Kinv, p.obs_uv[2 * o], p.obs_uv[2 * o + 1]);
+        const ViewRow vr = view_row(vp, R, t, p.cam_R0 + 9 * s, p.cam_t0 + 3 * s, p.g, lane & 1, p.obs_w ? p.obs_w + o : nullptr);
+        if ((lane & 1) == 0 && wfirst) sSlot[view] = s;
+        res = vr.res;
+        a0 = vr.a[0]; a1 = vr.a[1]; a2 = vr.a[2]; a3 = vr.a[3]; a4 = vr.a[4]; a5 = vr.a[5];
+        h0 = vr.h[0]; h1 = vr.h[1]; h2 = vr.h[2];
     }
 
     if (p.stamps) tq[1] = wall_clock64();
@@ -1190,17 +1138,14 @@ __global__ __launch_bounds__(64 * NWV, NWV > 1 ? 1 : (RMAX <= 24 ? 3 : 2)) void 
     bool ok = (q >= 1) && (bad == 0) && (q < p.n_chi2);
     if (ok) ok = (gam <= p.chi2[q]);
     if (lane == 0) {
-        p.rank[f] = rank;
-        p.gamma[f] = gam;
         // 1 accepted, 0 rejected by the gate, 2 rejected because the gate matrix was not SPD.
         // (No global counters: 2000 workgroups adding to one word serialise at ~13 ns each and
         // were 50 us of this kernel; the host sums the per-feature results instead.)
-        p.accepted[f] = ok ? 1 : (bad ? 2 : 0);
-        if (p.acc_h) { p.rank_h[f] = rank; p.acc_h[f] = ok ? 1 : (bad ? 2 : 0); }
+        const unsigned char code = ok ? 1 : (bad ? 2 : 0);
+        feature_verdict(p, f, rank, gam, code);
         if constexpr (SPLIT) {
             // the blocks inherit the track's gate result; their `rank` is what K5's row count 2 M - rank needs
             const SplitRec& sr = p.split[blockIdx.x];
-            const unsigned char code = ok ? 1 : (bad ? 2 : 0);
             for (int g = 0; g < sr.ng; ++g) if (sr.child[g] >= 0) { p.rank[sr.child[g]] = 3; p.accepted[sr.child[g]] = code; }
             p.rank[sr.wide] = R2 - n_wide_rows; p.accepted[sr.wide] = code;
         }

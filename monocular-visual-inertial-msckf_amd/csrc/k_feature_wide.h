@@ -6,9 +6,9 @@
 //   K4  the block [H_o | r_o], q x (6M + 1), row-major at blk_off[f]   reference MSCKF.py:581-588
 //
 // k_feature.h holds one measurement row per LANE, so 2M + 1 rows must fit one wavefront: 31 views.  Here a row belongs to a
-// THREAD of the workgroup (K1), the three column-pivoted Householder reflectors of H_f (2M x 3) are formed by the first wavefront
-// with two rows per lane (K2), and H_o = D - V Z with Z = T^T (V^T D) (3 x 6M; k_feature.h's sZ) is written to the stack by all
-// threads (K4).  At 64 views the block is 125 x 385 doubles: it lives in HBM, and the gate reads it from there.
+// THREAD of the workgroup (K1: view_row.h, the text k_feature calls), the three column-pivoted Householder reflectors of H_f (2M x 3)
+// are formed by the first wavefront with two rows per lane (K2), and H_o = D - V Z with Z = T^T (V^T D) (3 x 6M; k_feature.h's sZ) is
+// written to the stack by all threads (K4).  At 64 views the block is 125 x 385 doubles: it lives in HBM, and the gate reads it from there.
 //
 // The gate (K3): E = H_o P_sub and S = E H_o^T + sigma^2 I on the fp64 matrix cores (v_mfma_f64_16x16x4_f64; operand layout as in
 // k_gain.h: A lane -> (row lane & 15, k lane >> 4), B lane -> (k lane >> 4, column lane & 15), D register r of a lane -> (row
@@ -23,7 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wave_ops.h"
-#include "k_feature.h"            // FeatureArgs, wall_clock64 users
+#include "k_feature.h"            // FeatureArgs, feature_verdict, view_row.h
 
 namespace msckf {
 
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(FEATW_T) void k_feature_wide(FeatureWideArgs w) {
     const int M = p.view_ptr[f + 1] - v0;
     if (blockIdx.x == 0 && t < 8) static_cast<double*>(p.stack)[p.zero_idx + t] = 0.0;   // the stack's zero words (as k_feature's track 0)
     if (M < 1 || M > FEATW_MAXM) {            // (never sent by the host: nothing below may index past the carve-up)
-        if (t == 0) { p.rank[f] = 0; p.gamma[f] = 0.0; p.accepted[f] = 0; if (p.acc_h) { p.rank_h[f] = 0; p.acc_h[f] = 0; } }
+        if (t == 0) feature_verdict(p, f, 0, 0.0, 0);
         return;
     }
     const int R2 = 2 * M, C6 = 6 * M;
@@ -79,87 +79,25 @@ __global__ __launch_bounds__(FEATW_T) void k_feature_wide(FeatureWideArgs w) {
     double* sS = smem + FeatWideLayout::S;
 
     if (p.select && !(p.select[f] & 1)) {      // not in valid_features (MSCKF.py:453-455): no rows, not a rejection
-        if (t == 0) {
-            p.rank[f] = 0; p.gamma[f] = 0.0; p.accepted[f] = 3;
-            if (p.acc_h) { p.rank_h[f] = 0; p.acc_h[f] = 3; }
-        }
+        if (t == 0) feature_verdict(p, f, 0, 0.0, 3);
         return;
     }
     long long tq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (p.stamps) tq[0] = wall_clock64();
-    // ---------------- K1: one measurement row per thread (the arithmetic of k_feature.h, same order of operations) ------------
+    // ---------------- K1: one measurement row per thread (view_row.h) ------------
     if (t < R2) {
-        double res = 0.0, a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, h0 = 0, h1 = 0, h2 = 0;
         const int view = t >> 1;
         const int o = v0 + view;
         const int s = p.obs_slot[o];
         if ((t & 1) == 0) sSlot[view] = s;
         const double* R = p.cam_R + 9 * s;
         const double* tt = p.cam_t + 3 * s;
-        const double* R0 = p.cam_R0 + 9 * s;
-        const double* t0 = p.cam_t0 + 3 * s;
-        const double rho = p.idp_rho[f];
-        const double wx = rho * (p.idp_base[3 * f + 0] - tt[0]) + p.idp_m[3 * f + 0];
-        const double wy = rho * (p.idp_base[3 * f + 1] - tt[1]) + p.idp_m[3 * f + 1];
-        const double wz = rho * (p.idp_base[3 * f + 2] - tt[2]) + p.idp_m[3 * f + 2];
-        // Ci_f = R^T w   (MSCKF.py:516)
-        const double px = R[0] * wx + R[3] * wy + R[6] * wz;
-        const double py = R[1] * wx + R[4] * wy + R[7] * wz;
-        const double pz = R[2] * wx + R[5] * wy + R[8] * wz;
-        // W_f = R Ci_f + t (MSCKF.py:517)
-        const double Wx = R[0] * px + R[1] * py + R[2] * pz + tt[0];
-        const double Wy = R[3] * px + R[4] * py + R[5] * pz + tt[1];
-        const double Wz = R[6] * px + R[7] * py + R[8] * pz + tt[2];
-        const double u = p.obs_uv[2 * o], v = p.obs_uv[2 * o + 1];
-        double wgt = 1.0;
-        if (p.obs_w) wgt = p.obs_w[o];
-        const double zx = p.Kinv[0] * u + p.Kinv[1] * v + p.Kinv[2];
-        const double zy = p.Kinv[3] * u + p.Kinv[4] * v + p.Kinv[5];
-        const double zw = p.Kinv[6] * u + p.Kinv[7] * v + p.Kinv[8];
-        const double ia = 1.0 / pz;
-        const double jb = -px * (ia * ia);
-        const double jc = -py * (ia * ia);
-        const double izw = 1.0 / zw;
-        // u = [R0^T g ; (W_f - t0) x g]   (MSCKF.py:528-530)
-        const double gx = p.g[0], gy = p.g[1], gz = p.g[2];
-        const double u0 = R0[0] * gx + R0[3] * gy + R0[6] * gz;
-        const double u1 = R0[1] * gx + R0[4] * gy + R0[7] * gz;
-        const double u2 = R0[2] * gx + R0[5] * gy + R0[8] * gz;
-        const double ex = Wx - t0[0], ey = Wy - t0[1], ez = Wz - t0[2];
-        const double u3 = ey * gz - ez * gy;
-        const double u4 = ez * gx - ex * gz;
-        const double u5 = ex * gy - ey * gx;
-        const double den = u0 * u0 + u1 * u1 + u2 * u2 + u3 * u3 + u4 * u4 + u5 * u5;
-        double J0, J1, J2;   // this thread's row of J (Camera.py:57-58)
-        if ((t & 1) == 0) {
-            res = zx * izw - px * ia;
-            J0 = ia; J1 = 0.0; J2 = jb;
-            a0 = -jb * py; a1 = -ia * pz + jb * px; a2 = ia * py;          // J skew(Ci_f), row 0
-        } else {
-            res = zy * izw - py * ia;
-            J0 = 0.0; J1 = ia; J2 = jc;
-            a0 = ia * pz - jc * py; a1 = jc * px; a2 = -ia * px;           // row 1
-        }
-        // H_f = J R^T (this row);  H_x[:,3:] = -H_f   (Camera.py:62,66; MSCKF.py:536)
-        h0 = J0 * R[0] + J1 * R[1] + J2 * R[2];
-        h1 = J0 * R[3] + J1 * R[4] + J2 * R[5];
-        h2 = J0 * R[6] + J1 * R[7] + J2 * R[8];
-        a3 = -h0; a4 = -h1; a5 = -h2;
-        if (den > 1e-6) {      // observability-constrained projection (MSCKF.py:532-534)
-            const double au = a0 * u0 + a1 * u1 + a2 * u2 + a3 * u3 + a4 * u4 + a5 * u5;
-            const double aud = au * (1.0 / den);
-            a0 -= aud * u0; a1 -= aud * u1; a2 -= aud * u2;
-            a3 -= aud * u3; a4 -= aud * u4; a5 -= aud * u5;
-        }
-        // per-view noise: the view's rows of r, H_x and H_f times w_v = sigma / sigma_v, once and in front of everything else
-        if (p.obs_w) {
-            res *= wgt;
-            a0 *= wgt; a1 *= wgt; a2 *= wgt; a3 *= wgt; a4 *= wgt; a5 *= wgt;
-            h0 *= wgt; h1 *= wgt; h2 *= wgt;
-        }
-        sA[t * 6 + 0] = a0; sA[t * 6 + 1] = a1; sA[t * 6 + 2] = a2; sA[t * 6 + 3] = a3; sA[t * 6 + 4] = a4; sA[t * 6 + 5] = a5;
-        sV[t * 3 + 0] = h0; sV[t * 3 + 1] = h1; sV[t * 3 + 2] = h2;
-        sRes[t] = res;
+        const ViewPoint vp = view_point(R, tt, p.idp_base + 3 * f, p.idp_m + 3 * f, p.idp_rho[f], p.Kinv, p.obs_uv[2 * o], p.obs_uv[2 * o + 1]);
+        const ViewRow vr = view_row(vp, R, tt, p.cam_R0 + 9 * s, p.cam_t0 + 3 * s, p.g, t & 1, p.obs_w ? p.obs_w + o : nullptr);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) sA[t * 6 + a] = vr.a[a];
+        sV[t * 3 + 0] = vr.h[0]; sV[t * 3 + 1] = vr.h[1]; sV[t * 3 + 2] = vr.h[2];
+        sRes[t] = vr.res;
     }
     __syncthreads();
     if (p.stamps) tq[1] = wall_clock64();
@@ -397,10 +335,7 @@ __global__ __launch_bounds__(FEATW_T) void k_feature_wide(FeatureWideArgs w) {
         bool ok = (q >= 1) && (bad == 0) && (q < p.n_chi2);
         if (ok) ok = (gam <= p.chi2[q]);
         if (lane == 0) {
-            p.rank[f] = rank;
-            p.gamma[f] = gam;
-            p.accepted[f] = ok ? 1 : (bad ? 2 : 0);     // 1 accepted, 0 rejected by the gate, 2 the gate matrix was not SPD
-            if (p.acc_h) { p.rank_h[f] = rank; p.acc_h[f] = ok ? 1 : (bad ? 2 : 0); }
+            feature_verdict(p, f, rank, gam, ok ? 1 : (bad ? 2 : 0));     // 1 accepted, 0 rejected by the gate, 2 the gate matrix was not SPD
             if (p.stamps) { tq[7] = wall_clock64(); for (int i = 0; i < 8; ++i) p.stamps[8 * f + i] = tq[i]; }
         }
     }

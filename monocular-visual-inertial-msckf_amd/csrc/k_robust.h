@@ -1,9 +1,9 @@
 // Robust per-view weights in front of K1 (msckf_set_robust).  Not in the reference, whose only defence against
 // a bad observation is the gate (MSCKF.py:562-579), all or nothing per track.
 //
-// One thread per view of the tracks [0, F) of the sorted arrays.  It forms the view's two residual components exactly as K1
-// does (k_feature.h, "K1: one measurement row per lane": z / z_w - p_xy / p_z in normalised image coordinates, MSCKF.py:516,
-// Camera.py:54-58) from the batch's current inverse-depth points and the resident poses, whitens their norm with the view's
+// One thread per view of the tracks [0, F) of the sorted arrays.  It forms the view's two residual components from K1's own
+// point and observation (view_row.h's view_point: z / z_w - p_xy / p_z in normalised image coordinates, MSCKF.py:516,
+// Camera.py:54-58) of the batch's current inverse-depth points and the resident poses, whitens their norm with the view's
 // base weight b_v (sigma / sigma_v of msckf_set_view_sigma, else 1) and the global sigma,
 //     s_v = b_v |e_v| / sigma,      w_v = b_v phi(s_v)      (robust_weight.h),
 // and writes w_v where K1 reads FeatureArgs::obs_w from -- an array of the run's own: the base weights are read, never written,
@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "robust_weight.h"
+#include "view_row.h"
 
 namespace msckf {
 
@@ -53,23 +54,10 @@ __global__ __launch_bounds__(ROBUST_THREADS) void k_robust(RobustArgs p) {
     const double b = p.obs_b ? p.obs_b[o] : 1.0;
     if (p.select && !(p.select[f] & 1)) { p.w[o] = b; p.s[o] = 0.0; return; }
     const int sl = p.obs_slot[o];
-    const double* R = p.cam_R + 9 * sl;
-    const double* t = p.cam_t + 3 * sl;
-    const double rho = p.idp_rho[f];
-    const double wx = rho * (p.idp_base[3 * f + 0] - t[0]) + p.idp_m[3 * f + 0];
-    const double wy = rho * (p.idp_base[3 * f + 1] - t[1]) + p.idp_m[3 * f + 1];
-    const double wz = rho * (p.idp_base[3 * f + 2] - t[2]) + p.idp_m[3 * f + 2];
-    // Ci_f = R^T w   (MSCKF.py:516)
-    const double px = R[0] * wx + R[3] * wy + R[6] * wz;
-    const double py = R[1] * wx + R[4] * wy + R[7] * wz;
-    const double pz = R[2] * wx + R[5] * wy + R[8] * wz;
-    const double u = p.obs_uv[2 * o], v = p.obs_uv[2 * o + 1];
-    const double zx = p.Kinv[0] * u + p.Kinv[1] * v + p.Kinv[2];
-    const double zy = p.Kinv[3] * u + p.Kinv[4] * v + p.Kinv[5];
-    const double zw = p.Kinv[6] * u + p.Kinv[7] * v + p.Kinv[8];
-    const double ia = 1.0 / pz, izw = 1.0 / zw;
-    const double ex = zx * izw - px * ia;
-    const double ey = zy * izw - py * ia;
+    const ViewPoint q = view_point(p.cam_R + 9 * sl, p.cam_t + 3 * sl, p.idp_base + 3 * f, p.idp_m + 3 * f, p.idp_rho[f], p.Kinv,
+                                   p.obs_uv[2 * o], p.obs_uv[2 * o + 1]);
+    const double ex = q.zx * q.izw - q.px * q.ia;           // view_row's two residuals
+    const double ey = q.zy * q.izw - q.py * q.ia;
     const double sv = b * sqrt(ex * ex + ey * ey) / p.sigma;
     p.w[o] = b * robust_phi(p.loss, p.k, p.w_min, sv);
     p.s[o] = sv;

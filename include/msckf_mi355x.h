@@ -73,16 +73,27 @@ extern "C" {
 #define MSCKF_FLAG_BAND_ONLY 2      /* K5: tracks of more than 10 clone slots are NOT split: tracks of
                                        11 - 15 slots take the 90-column band tiles, wider ones the merge tree  */
 
+#define MSCKF_FLAG_WIDE_STORE 4     /* a context created with max_track > MSCKF_MAX_TRACK_ROW (fp64) gets the track store:
+                                       rows of max_track views.  Without it the msckf_tracks_* calls of such a context
+                                       answer MSCKF_ERR_ARG, as they did before the flag existed; with max_track <=
+                                       MSCKF_MAX_TRACK_ROW it changes nothing.  With MSCKF_DTYPE_F32 and max_track >
+                                       MSCKF_MAX_TRACK_ROW: msckf_create answers MSCKF_ERR_ARG (the f32 stack keeps
+                                       MSCKF_MAX_TRACK views a track, rows of more could never be loaded)          */
+
 #define MSCKF_DTYPE_F64 0
 #define MSCKF_DTYPE_F32 1
 
 #define MSCKF_MAX_TRACK 31          /* views of a track the NARROW K1-K4 kernels take (k_feature: one lane per measurement
                                        row, 2M+1 rows fit one wavefront); longer tracks go to k_feature_wide            */
-#define MSCKF_MAX_TRACK_ROW 32      /* views a row of the track store may hold: a track of MSCKF_MAX_TRACK views can take
-                                       the newest clone's view (msckf_tracks_frame); on a context created with
-                                       max_track <= MSCKF_MAX_TRACK_ROW a batch track still holds at most MSCKF_MAX_TRACK */
+#define MSCKF_MAX_TRACK_ROW 32      /* views a row of a NARROW context's track store may hold (max_track <= this): a track of
+                                       MSCKF_MAX_TRACK views can take the newest clone's view (msckf_tracks_frame); a batch
+                                       track of such a context still holds at most MSCKF_MAX_TRACK.  The per-row kernels
+                                       give such a row a 32-lane group.  Above it a context is a wide-track context    */
 #define MSCKF_MAX_TRACK_WIDE 64     /* views of a batch track on a context created with max_track > MSCKF_MAX_TRACK_ROW
-                                       (fp64 only).  k_feature_wide keeps, per workgroup, the track's D, V, Z, r rows and the
+                                       (fp64 only), and with MSCKF_FLAG_WIDE_STORE of a row of its track store (one
+                                       wavefront per row: a row and a batch track have ONE limit there, max_track, and a
+                                       full row refuses a further view as a 32-view row does).
+                                       k_feature_wide keeps, per workgroup, the track's D, V, Z, r rows and the
                                        packed lower triangle of the gate matrix with the residual row in LDS:
                                        2 V^2 + 43.5 V + 1105 doubles at V views = 12081 doubles = 94.4 KiB at 64 (the
                                        160 KiB of a CU would hold V = 88).  64 is where the other holders of a track end:
@@ -101,7 +112,8 @@ typedef struct msckf_config {
                                        batch limit.  MSCKF_MAX_TRACK_ROW: the track store's rows hold that many views, the
                                        batch limit stays MSCKF_MAX_TRACK.  More: the batch limit (fp64; an f32 context keeps
                                        MSCKF_MAX_TRACK), tracks of more than MSCKF_MAX_TRACK views take k_feature_wide and the
-                                       merge tree; such a context has no track store (msckf_tracks_*: MSCKF_ERR_ARG) and
+                                       merge tree; such a context has a track store on request only (MSCKF_FLAG_WIDE_STORE:
+                                       rows of max_track views; without the flag msckf_tracks_*: MSCKF_ERR_ARG) and
                                        a batch with such a track takes no part in a sharded update (MSCKF_ERR_STATE)   */
     int32_t leaf_rows;              /* 0 = default; target stacked rows per QR leaf         */
     int32_t merge_arity;            /* 0 = default; max children per QR tree node           */
@@ -461,7 +473,8 @@ int msckf_get_rows_gate(msckf_ctx* ctx, double* gamma, int32_t* applied);
  * The feature batch is the last input of the resident loop that depends on the clone poses: every Line.base is the
  * clone's own position array (MSCKF.py:410, :430-431) and every InverseDepthPoint.base that of the clone the track was
  * created in (geometry.py:55), so both move with each injection.  The store keeps every floating-point field of the
- * tracks in HBM (fp64 in both dtypes; capacity max_features tracks x max_track views, allocated on first use) and which
+ * tracks in HBM (fp64 in both dtypes; capacity max_features tracks x max_track views, allocated on first use; on a context with
+ * max_track > MSCKF_MAX_TRACK_ROW only with MSCKF_FLAG_WIDE_STORE, else every call of this section answers MSCKF_ERR_ARG) and which
  * track has views in which clone slots on the host, inside the context.  A frame sends its new keypoints
  * (msckf_tracks_observe) and asks for a batch by track id (msckf_tracks_load); the bases are resolved on the device from
  * the resident clone positions.  Works on any context with a state; the "newest clone" is slot N - 1.

@@ -10,6 +10,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 FLAG_TREE_PLAN = 1
 FLAG_BAND_ONLY = 2      # msckf_config.flags: long tracks are not split (one Householder plan for every track: 90-column tiles / merge tree)
+FLAG_WIDE_STORE = 4     # msckf_config.flags: a context with max_track > MAX_TRACK_ROW (fp64) gets the track store, rows of max_track views
 LIB_PATH = os.environ.get("MSCKF_LIB") or os.path.join(_HERE, "libmsckf_mi355x.so")   # MSCKF_LIB: A/B builds
 ABI_VERSION = 2
 DTYPE_F64, DTYPE_F32 = 0, 1
@@ -20,8 +21,9 @@ COMM_ID_BYTES = 128
 MAX_TRACK = 31
 MAX_ROWS = 32           # MSCKF_MAX_ROWS: rows of one msckf_run_rows
 FIX_POSITION, FIX_VELOCITY = 1, 2
-MAX_TRACK_ROW = 32      # MSCKF_MAX_TRACK_ROW: views a row of the track store may hold (a batch track: MAX_TRACK)
-MAX_TRACK_WIDE = 64     # MSCKF_MAX_TRACK_WIDE: views of a batch track on a context created with max_track > MAX_TRACK_ROW (fp64)
+MAX_TRACK_ROW = 32      # MSCKF_MAX_TRACK_ROW: views a row of a narrow context's track store may hold (a batch track: MAX_TRACK)
+MAX_TRACK_WIDE = 64     # MSCKF_MAX_TRACK_WIDE: views of a batch track on a context created with max_track > MAX_TRACK_ROW (fp64),
+                        # and of a row of its track store (FLAG_WIDE_STORE)
 
 # every symbol include/msckf_mi355x.h declares
 SYMBOLS = [

@@ -92,24 +92,32 @@ class UpdateEngine:
     """One context on one MI355X.  Not thread-safe (one engine per host thread)."""
 
     def __init__(self, max_clones: int = 30, max_features: int = 4096, max_track: int = 30,
-                 device: int = 0, leaf_rows: int = 0, merge_arity: int = 0, plan: str = "auto", dtype: str = "f64"):
+                 device: int = 0, leaf_rows: int = 0, merge_arity: int = 0, plan: str = "auto", dtype: str = "f64",
+                 wide_store: bool = False):
         """plan: "auto" = band pipeline (k_sweep) for tracks of up to 10 clone slots; longer ones are split into <= 10-slot
         blocks for that pipeline + a few remainder rows; "band" = no split: 90-column band tiles for tracks of
         11 - 15 slots, the merge tree beyond; "tree" = always the merge tree (A/B, tests).
         dtype: "f64" = the reference's arithmetic (parity 1e-8); "f32" = fp32 storage of the stacked system and
-        the Joseph covariance update on the f32 matrix cores (BASELINE.json configs[4]; tolerance in DESIGN.md)."""
-        self._lib = _ffi.load()
+        the Joseph covariance update on the f32 matrix cores (BASELINE.json configs[4]; tolerance in DESIGN.md).
+        wide_store: with `max_track` > 32 the engine has a track store (`tracks_*`, `load_tracks*`) only on request: rows of
+        `max_track` views, which is also the batch limit (fp64 only; `MSCKF_FLAG_WIDE_STORE`).  Without it such an engine
+        answers `ERR_ARG` to every store call; with `max_track` <= 32 it changes nothing."""
         # (up to MAX_TRACK: the batch limit; MAX_TRACK_ROW: rows of the track store only, a batch track holds MAX_TRACK; beyond: the
-        #  batch limit of a context without a track store, tracks of more than MAX_TRACK views on the wide K1-K4 kernel)
+        #  batch limit, tracks of more than MAX_TRACK views on the wide K1-K4 kernel, and with wide_store the rows of the store)
         if max_track > _ffi.MAX_TRACK_WIDE:
             raise ValueError(f"max_track {max_track} > {_ffi.MAX_TRACK_WIDE}")
         if plan not in ("auto", "band", "tree"):
             raise ValueError("plan must be 'auto', 'band' or 'tree'")
         if dtype not in ("f64", "f32"):
             raise ValueError("dtype must be 'f64' or 'f32'")
+        if wide_store and dtype == "f32" and max_track > _ffi.MAX_TRACK_ROW:
+            raise ValueError(f"wide_store with dtype 'f32' and max_track {max_track} > {_ffi.MAX_TRACK_ROW}: the f32 stack takes "
+                             f"tracks of {_ffi.MAX_TRACK} views, rows of more could never be loaded")
+        self._lib = _ffi.load()               # (every argument check stands in front of the library)
         self.dtype = dtype
         cfg = _ffi.Config(_ffi.ABI_VERSION, device, max_clones, max_features, max_track, leaf_rows, merge_arity,
-                          {"tree": _ffi.FLAG_TREE_PLAN, "band": _ffi.FLAG_BAND_ONLY}.get(plan, 0), _ffi.DTYPE_F32 if dtype == "f32" else _ffi.DTYPE_F64, 0)
+                          {"tree": _ffi.FLAG_TREE_PLAN, "band": _ffi.FLAG_BAND_ONLY}.get(plan, 0) | (_ffi.FLAG_WIDE_STORE if wide_store else 0),
+                          _ffi.DTYPE_F32 if dtype == "f32" else _ffi.DTYPE_F64, 0)
         h = C.c_void_p()
         rc = self._lib.msckf_create(C.byref(h), C.byref(cfg))
         if rc != 0:
@@ -727,7 +735,7 @@ class UpdateEngine:
     def track_descriptor(self, track_id: int):
         """(match row (D,), per-view descriptors (M, D)) of one track as they stand on the device, fp32.  Blocking."""
         row = np.zeros(_ffi.DESC_DIM, dtype=np.float32)
-        views = np.zeros(_ffi.MAX_TRACK_ROW * _ffi.DESC_DIM, dtype=np.float32)
+        views = np.zeros(max(self.max_track, _ffi.MAX_TRACK_ROW) * _ffi.DESC_DIM, dtype=np.float32)
         M = C.c_int32(0)
         self._check(self._lib.msckf_tracks_descriptor(self._h, int(track_id), _ffi.dptr(row), C.addressof(M), _ffi.dptr(views)),
                     allow_noop=False)
@@ -764,7 +772,7 @@ class UpdateEngine:
     def track(self, track_id: int) -> dict:
         """One track as it stands on the device (waits for the stream): `slots, uv, dir, conf, line_base, idp_base,
         idp_m, idp_rho, anchor_slot` (-1 once the anchor clone was removed: the base is frozen)."""
-        V = _ffi.MAX_TRACK_ROW
+        V = max(self.max_track, _ffi.MAX_TRACK_ROW)
         M, anchor = C.c_int32(0), C.c_int32(0)
         rho = C.c_double(0)
         slots = np.zeros(V, dtype=np.int32)

@@ -97,10 +97,32 @@ struct TrackEmitArgs {
 
 constexpr int TRACK_THREADS = 256;
 
-// One 32-lane group per candidate; lane v carries view v (a row holds at most 31).
+// The per-row kernels give a row a group of G lanes, lane v carrying view v.  G = 32: two rows share a wavefront, each takes
+// its half of the wavefront's ballot as a 32-bit mask (the store of a context with max_track <= 32).  G = 64: a wavefront
+// per row, the whole 64-bit ballot is the row's (a context created with MSCKF_FLAG_WIDE_STORE, rows of up to 64 views).
+template <int G> struct TrackGroup;
+template <> struct TrackGroup<32> {
+    using mask_t = unsigned;
+    static __device__ __forceinline__ mask_t mine(unsigned long long b) { return (unsigned)(b >> (threadIdx.x & 32)); }
+    static __device__ __forceinline__ mask_t below(int v) { return (1u << v) - 1u; }
+    static __device__ __forceinline__ int popc(mask_t m) { return __popc(m); }
+    static __device__ __forceinline__ int ffs(mask_t m) { return __ffs(m); }
+};
+template <> struct TrackGroup<64> {
+    using mask_t = unsigned long long;
+    static __device__ __forceinline__ mask_t mine(unsigned long long b) { return b; }
+    static __device__ __forceinline__ mask_t below(int v) { return (1ull << v) - 1ull; }
+    static __device__ __forceinline__ int popc(mask_t m) { return __popcll(m); }
+    static __device__ __forceinline__ int ffs(mask_t m) { return __ffsll(m); }
+};
+constexpr int track_group_log2(int G) { return G == 64 ? 6 : 5; }
+
+// One G-lane group per candidate; lane v carries view v (v < M <= V <= G).
+template <int G>
 __global__ __launch_bounds__(TRACK_THREADS) void k_track_emit(TrackEmitArgs p) {
-    const int v = threadIdx.x & 31;
-    const int f = blockIdx.x * (TRACK_THREADS / 32) + (threadIdx.x >> 5);
+    static_assert(G == 32 || G == 64, "a row's group is half a wavefront or a whole one");
+    const int v = threadIdx.x & (G - 1);
+    const int f = blockIdx.x * (TRACK_THREADS / G) + (threadIdx.x >> track_group_log2(G));
     if (f >= p.F) return;
     const TrackEmitRec r = p.rec[f];
     const size_t row = (size_t)r.row;
@@ -117,7 +139,8 @@ __global__ __launch_bounds__(TRACK_THREADS) void k_track_emit(TrackEmitArgs p) {
         }
         p.line_conf[out] = p.s.conf[e];
     }
-    // (the head of the track on lanes that are free in the shortest track as well as busy in the longest)
+    // (the head of the track on lanes that are free in the shortest track as well as busy in the longest; in a row of 64 views
+    //  every lane carries a view, these eight among them)
     if (v < 3) {
         const int an = p.s.anchor[row];
         p.base_raw[3 * (size_t)f + v] = an >= 0 ? p.cam_t[3 * (size_t)an + v] : p.s.frozen[3 * row + v];
@@ -138,10 +161,13 @@ struct TrackDropArgs {
     short remap[224];             // old slot -> new slot, -1: removed (a window holds at most 221 clones)
 };
 
-// One 32-lane group per track: drop the views of removed clones, close the gaps, renumber, freeze the anchor.
+// One G-lane group per track: drop the views of removed clones, close the gaps, renumber, freeze the anchor.
+template <int G>
 __global__ __launch_bounds__(TRACK_THREADS) void k_track_drop(TrackDropArgs p) {
-    const int v = threadIdx.x & 31;
-    const int g = blockIdx.x * (TRACK_THREADS / 32) + (threadIdx.x >> 5);
+    static_assert(G == 32 || G == 64, "a row's group is half a wavefront or a whole one");
+    using Grp = TrackGroup<G>;
+    const int v = threadIdx.x & (G - 1);
+    const int g = blockIdx.x * (TRACK_THREADS / G) + (threadIdx.x >> track_group_log2(G));
     const bool live = g < p.n;
     const size_t row = live ? (size_t)p.rows[g] : 0;
     const int M = live ? p.s.count[row] : 0;
@@ -156,19 +182,20 @@ __global__ __launch_bounds__(TRACK_THREADS) void k_track_drop(TrackDropArgs p) {
         d0 = p.s.dir[3 * e]; d1 = p.s.dir[3 * e + 1]; d2 = p.s.dir[3 * e + 2];
         cf = p.s.conf[e];
     }
-    // the group's half of the wavefront's ballot; a view moves down by the number of dropped views in front of it.  (Every
-    // lane of the wavefront has read its view by now: the stores below wait for the loads above.)
+    // the group's share of the wavefront's ballot (G = 32: its half; G = 64: all of it); a view moves down by the number of
+    // dropped views in front of it.  (Every lane of the wavefront has read its view by now: the stores below wait for the
+    // loads above.)
     const unsigned long long b = __ballot(keep);
-    const unsigned mine = (unsigned)(b >> (threadIdx.x & 32));
+    const typename Grp::mask_t mine = Grp::mine(b);
     if (keep) {
-        const size_t w = row * p.s.V + __popc(mine & ((1u << v) - 1u));
+        const size_t w = row * p.s.V + Grp::popc(mine & Grp::below(v));
         p.s.uv[2 * w] = u0; p.s.uv[2 * w + 1] = u1;
         p.s.dir[3 * w] = d0; p.s.dir[3 * w + 1] = d1; p.s.dir[3 * w + 2] = d2;
         p.s.conf[w] = cf;
         p.s.slot[w] = ns;
     }
     if (live && v == 0) {
-        p.s.count[row] = __popc(mine);
+        p.s.count[row] = Grp::popc(mine);
         const int an = p.s.anchor[row];
         if (an >= 0) {
             const int na = p.remap[an];
@@ -197,12 +224,16 @@ struct TrackFrameArgs {
     unsigned char* result;        // [n] (pinned host memory) 0 appended, 1 epipolar failure, 2 homography failure, 4 created
 };
 
-// One 32-lane group per pair; lane v tests stored view v (a tested row holds at most 31).  The group's half of the
-// wavefront's ballot gives the first failing view, where the reference breaks (:369, :390).  Lane 0 appends: position
-// `pos` is read by no lane (v < pos), and every pair has a row of its own.
+// One G-lane group per pair; lane v tests stored view v (a tested row holds at most G - 1: the mirror refuses a full row).
+// The group's share of the wavefront's ballot gives the first failing view, where the reference breaks (:369, :390).  Lane
+// 0 appends: position `pos` (<= V - 1) is read by no lane (v < pos), and every pair has a row of its own.  Every lane
+// reaches both ballots: the early exit stands behind them.
+template <int G>
 __global__ __launch_bounds__(TRACK_THREADS) void k_track_frame(TrackFrameArgs p) {
-    const int v = threadIdx.x & 31;
-    const int g = blockIdx.x * (TRACK_THREADS / 32) + (threadIdx.x >> 5);
+    static_assert(G == 32 || G == 64, "a row's group is half a wavefront or a whole one");
+    using Grp = TrackGroup<G>;
+    const int v = threadIdx.x & (G - 1);
+    const int g = blockIdx.x * (TRACK_THREADS / G) + (threadIdx.x >> track_group_log2(G));
     const bool live = g < p.n;
     TrackObsRec r{};
     if (live) r = p.rec[g];
@@ -217,9 +248,9 @@ __global__ __launch_bounds__(TRACK_THREADS) void k_track_frame(TrackFrameArgs p)
                                r.u, r.v, p.thr_epipolar, p.thr_homography);
     }
     const unsigned long long bf = __ballot(code != 0), bh = __ballot(code == 2);
-    const unsigned fails = (unsigned)(bf >> (threadIdx.x & 32)), homs = (unsigned)(bh >> (threadIdx.x & 32));
+    const typename Grp::mask_t fails = Grp::mine(bf), homs = Grp::mine(bh);
     if (!live || v != 0) return;
-    const int first = fails ? __ffs(fails) - 1 : -1;
+    const int first = fails ? Grp::ffs(fails) - 1 : -1;
     p.fail_view[g] = first;
     p.result[g] = r.fresh ? 4 : first < 0 ? 0 : ((homs >> first) & 1u) ? 2 : 1;
     if (first < 0) track_store_view(p.s, r, p.slot, R2, p.Kinv);

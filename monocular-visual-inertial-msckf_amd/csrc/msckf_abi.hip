@@ -2213,6 +2213,13 @@ int stage_release(msckf_ctx* c, PinStage& s) {
     return MSCKF_OK;
 }
 
+// A context created for wide tracks (max_track > MSCKF_MAX_TRACK_ROW) has a track store only on request: every msckf_tracks_*
+// entry point answers MSCKF_ERR_ARG without MSCKF_FLAG_WIDE_STORE, as it did before the flag existed.
+inline bool no_track_store(const msckf_ctx* c) { return c->maxV > MSCKF_MAX_TRACK_ROW && !(c->cfg.flags & MSCKF_FLAG_WIDE_STORE); }
+// The per-row kernels of k_tracks.h: a 32-lane group per row, or a wavefront per row where the rows hold more than 32 views.
+inline bool tracks_wide_rows(const msckf_ctx* c) { return c->maxV > MSCKF_MAX_TRACK_ROW; }
+inline dim3 track_grid(int n, int G) { return dim3((n + TRACK_THREADS / G - 1) / (TRACK_THREADS / G)); }
+
 void tracks_clear(msckf_ctx* c) {
     c->mirror.clear();
     c->batch_from_store = false;
@@ -2264,7 +2271,8 @@ int launch_track_emit(msckf_ctx* c, const TrackEmitSrc* src, int F, int sumM, co
     a.rho_raw = reinterpret_cast<double*>(draw + raw.r_rho);
     a.line_base = ptr<double>(c->dLineBase); a.line_dir = ptr<double>(c->dLineDir); a.line_conf = ptr<double>(c->dLineConf);
     a.lost_for = ptr<int>(c->dLostFor); a.tracked_for = ptr<int>(c->dTrackedFor); a.row_sorted = ptr<int>(c->dTrkRowSorted);
-    hipLaunchKernelGGL(k_track_emit, dim3((F + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
+    if (tracks_wide_rows(c)) hipLaunchKernelGGL(k_track_emit<64>, track_grid(F, 64), dim3(TRACK_THREADS), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_track_emit<32>, track_grid(F, 32), dim3(TRACK_THREADS), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     return stage_release(c, c->trk_load_stage);
 }
@@ -2294,7 +2302,8 @@ int tracks_drop_clones(msckf_ctx* c, const std::vector<char>& drop) {
         hipLaunchKernelGGL(k_desc_drop, dim3(a.n), dim3(64), 0, c->stream, c->desc, a);
         HIPCHK(c, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_track_drop, dim3((a.n + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
+    if (tracks_wide_rows(c)) hipLaunchKernelGGL(k_track_drop<64>, track_grid(a.n, 64), dim3(TRACK_THREADS), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_track_drop<32>, track_grid(a.n, 32), dim3(TRACK_THREADS), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));                     // (`rows` is pageable memory; the call is a blocking one anyway)
     c->mirror.drop_clones(a.remap);
@@ -2334,6 +2343,8 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     if (cfg->max_track < 1 || cfg->max_track > MSCKF_MAX_TRACK_WIDE || cfg->max_clones < 1 || cfg->max_features < 0)
         return MSCKF_ERR_ARG;
     if (cfg->dtype != MSCKF_DTYPE_F64 && cfg->dtype != MSCKF_DTYPE_F32) return MSCKF_ERR_ARG;
+    // (rows of more than MSCKF_MAX_TRACK_ROW views could never be loaded: the f32 stack keeps MSCKF_MAX_TRACK views a track)
+    if ((cfg->flags & MSCKF_FLAG_WIDE_STORE) && cfg->dtype == MSCKF_DTYPE_F32 && cfg->max_track > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || cfg->device < 0 || cfg->device >= n) return MSCKF_ERR_NO_DEVICE;
     msckf_ctx* c = new msckf_ctx();
@@ -2341,7 +2352,8 @@ int msckf_create(msckf_ctx** out, const msckf_config* cfg) {
     c->device = cfg->device;
     c->maxN = cfg->max_clones; c->maxF = cfg->max_features; c->maxV = cfg->max_track;
     // a batch track: up to MSCKF_MAX_TRACK views on the narrow kernels; a context created for more (fp64) takes up to max_track
-    // of them on k_feature_wide.  (MSCKF_MAX_TRACK_ROW sizes the rows of the track store only; the f32 stack has no wide kernel)
+    // of them on k_feature_wide.  (MSCKF_MAX_TRACK_ROW sizes the rows of a narrow context's track store only; with
+    // MSCKF_FLAG_WIDE_STORE a wide context's rows hold max_track views, its batch limit; the f32 stack has no wide kernel)
     c->maxM = (cfg->max_track > MSCKF_MAX_TRACK_ROW && cfg->dtype == MSCKF_DTYPE_F64) ? cfg->max_track : std::min<int>(cfg->max_track, MSCKF_MAX_TRACK);
     if (hipSetDevice(c->device) != hipSuccess) { delete c; return MSCKF_ERR_NO_DEVICE; }
     hipDeviceProp_t prop{};
@@ -3768,14 +3780,14 @@ static int tracks_load_rows(msckf_ctx* c, int F, const std::vector<int>& rows, c
 }
 
 int msckf_tracks_reset(msckf_ctx* c) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c) return MSCKF_ERR_ARG;
     tracks_clear(c);
     return MSCKF_OK;
 }
 
 int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const double* uv, const double* score) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || n < 0) return MSCKF_ERR_ARG;
     if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
     if (n == 0) return MSCKF_OK;
@@ -3804,7 +3816,7 @@ int msckf_tracks_observe(msckf_ctx* c, int32_t n, const int32_t* ids, const doub
 }
 
 int msckf_tracks_remove(msckf_ctx* c, int32_t n, const int32_t* ids) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || n < 0 || (n > 0 && !ids)) return MSCKF_ERR_ARG;
     if (int rc = c->mirror.remove(ids, n)) return rc;
     tracks_rows_freed(c, (size_t)n);
@@ -3812,7 +3824,7 @@ int msckf_tracks_remove(msckf_ctx* c, int32_t n, const int32_t* ids) {
 }
 
 int msckf_tracks_load(msckf_ctx* c, int32_t F, const int32_t* ids, const int32_t* lost_for, const int32_t* tracked_for) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || F < 0 || F > c->maxF) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     if (F > 0 && (!ids || !lost_for || !tracked_for)) return MSCKF_ERR_ARG;
@@ -3859,7 +3871,8 @@ static int tracks_frame_impl(msckf_ctx* c, const msckf_frame_params* fp, int32_t
         std::memcpy(a.Kinv, c->Kinv, sizeof(a.Kinv));
         a.thr_epipolar = fp->epipolar_threshold; a.thr_homography = fp->homography_threshold;
         a.fail_view = reinterpret_cast<int*>(img + o_fv); a.result = reinterpret_cast<unsigned char*>(img + o_res);
-        hipLaunchKernelGGL(k_track_frame, dim3((n + TRACK_THREADS / 32 - 1) / (TRACK_THREADS / 32)), dim3(TRACK_THREADS), 0, c->stream, a);
+        if (tracks_wide_rows(c)) hipLaunchKernelGGL(k_track_frame<64>, track_grid(n, 64), dim3(TRACK_THREADS), 0, c->stream, a);
+        else hipLaunchKernelGGL(k_track_frame<32>, track_grid(n, 32), dim3(TRACK_THREADS), 0, c->stream, a);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));                 // the mirror needs the results: the call blocks
         for (int i = 0; i < n; ++i) {
@@ -3875,7 +3888,7 @@ static int tracks_frame_impl(msckf_ctx* c, const msckf_frame_params* fp, int32_t
 
 int msckf_tracks_frame(msckf_ctx* c, const msckf_frame_params* fp, int32_t n, const int32_t* ids, const double* uv,
                        const double* score, uint8_t* result, int32_t* fail_view) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     return tracks_frame_impl(c, fp, n, ids, uv, score, result, fail_view, false);
 }
 
@@ -4024,7 +4037,7 @@ static bool uv_finite(const double* uv, int32_t n) {
 // msckf_tracks_match (uv null: no keypoints, so no window) and msckf_tracks_match_at
 static int tracks_match_impl(msckf_ctx* c, double min_cos, int32_t D, int32_t n, const float* desc, const double* uv, bool with_uv,
                              int32_t* track_id_out, float* sim_out) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || n < 0 || (n > 0 && !track_id_out)) return MSCKF_ERR_ARG;
     if (with_uv && n > 0 && (!uv || !uv_finite(uv, n))) return MSCKF_ERR_ARG;
     if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
@@ -4054,7 +4067,7 @@ int msckf_tracks_match_at(msckf_ctx* c, double min_cos, int32_t D, int32_t n, co
 }
 
 int msckf_tracks_set_match_options(msckf_ctx* c, const msckf_match_options* o) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c) return MSCKF_ERR_ARG;
     if (!o) { c->match_opt = msckf_match_options{}; return MSCKF_OK; }
     if (!(o->search_radius >= 0.0) || !(o->min_margin >= 0.0)) return MSCKF_ERR_ARG;       // negative or NaN: nothing changed
@@ -4063,7 +4076,7 @@ int msckf_tracks_set_match_options(msckf_ctx* c, const msckf_match_options* o) {
 }
 
 int msckf_tracks_match_report(msckf_ctx* c, int32_t* T_out, int32_t* ids_out, uint8_t* why_out, int32_t cap) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || !T_out || cap < 0) return MSCKF_ERR_ARG;
     msckf_ctx::MatchReport& rep = c->match_rep;
     const size_t T = rep.ids.size();
@@ -4093,7 +4106,7 @@ int msckf_tracks_match_report(msckf_ctx* c, int32_t* T_out, int32_t* ids_out, ui
 
 int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t n, const float* desc, const double* uv,
                              const double* score, int32_t* ids_out, uint8_t* result, int32_t* fail_view, float* sim_out) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || !mp || n < 0) return MSCKF_ERR_ARG;
     if (!c->have_state || c->N < 1) return MSCKF_ERR_STATE;
     if (n == 0) return MSCKF_NOOP;                                   // MSCKF.py:286
@@ -4156,7 +4169,7 @@ int msckf_tracks_match_frame(msckf_ctx* c, const msckf_match_params* mp, int32_t
 }
 
 int msckf_tracks_descriptor(msckf_ctx* c, int32_t id, float* row, int32_t* M_out, float* views) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c) return MSCKF_ERR_ARG;
     const int at = c->mirror.row_of(id);
     if (at < 0) return MSCKF_ERR_ARG;
@@ -4175,7 +4188,7 @@ int msckf_tracks_descriptor(msckf_ctx* c, int32_t id, float* row, int32_t* M_out
 }
 
 int msckf_tracks_load_where(msckf_ctx* c, int32_t n_slots, const int32_t* slots, int32_t* F_out, int32_t* ids_out, int32_t cap) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || n_slots < 0 || cap < 0 || !F_out || (n_slots > 0 && !slots) || (cap > 0 && !ids_out)) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     std::vector<char> want(std::max(c->N, 1), n_slots == 0);
@@ -4201,7 +4214,7 @@ int msckf_tracks_load_where(msckf_ctx* c, int32_t n_slots, const int32_t* slots,
 }
 
 int msckf_tracks_counters(msckf_ctx* c, int32_t n, const int32_t* ids, int32_t* lost_for, int32_t* tracked_for) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || n < 0 || (n > 0 && !ids)) return MSCKF_ERR_ARG;
     for (int i = 0; i < n; ++i) if (c->mirror.row_of(ids[i]) < 0) return MSCKF_ERR_ARG;
     for (int i = 0; i < n; ++i) {
@@ -4213,7 +4226,7 @@ int msckf_tracks_counters(msckf_ctx* c, int32_t n, const int32_t* ids, int32_t* 
 }
 
 int msckf_tracks_clone_views(msckf_ctx* c, int32_t* views) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || (c->N > 0 && !views)) return MSCKF_ERR_ARG;
     if (!c->have_state) return MSCKF_ERR_STATE;
     for (int s = 0; s < c->N; ++s) views[s] = 0;
@@ -4226,7 +4239,7 @@ int msckf_tracks_clone_views(msckf_ctx* c, int32_t* views) {
 
 int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, double* uv, double* dir, double* conf,
                      double* line_base, double* idp_base, double* idp_m, double* idp_rho, int32_t* anchor_slot) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c) return MSCKF_ERR_ARG;
     const int row = c->mirror.row_of(id);
     if (row < 0) return MSCKF_ERR_ARG;
@@ -4265,7 +4278,7 @@ int msckf_tracks_get(msckf_ctx* c, int32_t id, int32_t* M_out, int32_t* slots, d
 }
 
 int msckf_tracks_count(msckf_ctx* c, int32_t* n_tracks, int32_t* n_views) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c) return MSCKF_ERR_ARG;
     if (n_tracks) *n_tracks = (int32_t)c->mirror.n_tracks();
     if (n_views) *n_views = (int32_t)c->mirror.n_views();
@@ -4273,7 +4286,7 @@ int msckf_tracks_count(msckf_ctx* c, int32_t* n_tracks, int32_t* n_views) {
 }
 
 int msckf_tracks_dropped(msckf_ctx* c, int32_t* ids, int32_t cap) {
-    if (c && c->maxV > MSCKF_MAX_TRACK_ROW) return MSCKF_ERR_ARG;      // (a context created for wide tracks has no track store)
+    if (c && no_track_store(c)) return MSCKF_ERR_ARG;                  // (a wide-track context created without MSCKF_FLAG_WIDE_STORE)
     if (!c || cap < 0 || (cap > 0 && !ids)) return MSCKF_ERR_ARG;
     const int n = (int)c->mirror.dropped().size();
     if (n > 0 && cap > 0) std::memcpy(ids, c->mirror.dropped().data(), (size_t)std::min(n, (int)cap) * 4);

@@ -257,6 +257,68 @@ typedef struct msckf_robust_params {
 int msckf_set_robust(msckf_ctx* ctx, const msckf_robust_params* params);
 int msckf_get_view_weights(msckf_ctx* ctx, double* w, double* s, int32_t* n_down);
 
+/* ---- known landmarks: a prior on a track's point (NOT in the reference) --- *
+ * Every track of the reference is a track of an unknown point: K2 projects [r | H_x] onto the left null space
+ * of H_f (MSCKF.py:554-559), and a surveyed fiducial or a map point loses its position there.  A Gaussian
+ * prior p ~ N(pbar, Sigma_p) on the point of track j is three more rows in front of that projection,
+ *     [ H_f     ]     [ H_x ]     [ r                      ]      W^T W = Sigma_p^-1  (W = L^-1, Sigma_p = L L^T)
+ *     [ sigma W ]     [ 0   ]     [ sigma W (pbar - p_lin) ]      p_lin = idp_base + idp_m / idp_rho
+ * with noise sigma^2 I like every other row: the left null space of the (2M + 3) x 3 block has 2M columns, the
+ * projected noise is sigma^2 I again, and the gate (2M degrees of freedom), K5 and K6-K7 are the code that runs
+ * without priors.  It is the EKF update with residual r - H_f (pbar - p_lin), Jacobian H_x and noise
+ * sigma^2 I + H_f Sigma_p H_f^T; a track of ONE view, which gives no rows without a prior, gives two with one.
+ * Units: the prior's columns are K1's H_f as it stands, the block whose negative stands in the clone's position
+ * columns (Camera.py:62, :66, MSCKF.py:536), so a shift of the point and the opposite shift of every observing
+ * clone are the same thing to the filter; the reference's rho-scaled geometry is kept as it is.
+ * Prior rows are not touched by per-view noise or the robust loss: those belong to views.  A prior so loose that
+ * K2's rank test finds fewer than three pivots on the augmented block is not stacked: the track is rejected.
+ *
+ * MSCKF_PRIOR_AT_MEAN linearises a prior track at the prior's mean: rho' = 1 / |pbar - base|,
+ * m' = (pbar - base) rho' stand in for the track's m, rho in everything that forms the run's K1 terms (the
+ * robust weights' residual norms included).  Where |pbar - base| is not finite or 0 the track keeps its own
+ * point.  The batch's m / rho (and the track store's rows) are never overwritten.
+ *
+ * msckf_set_point_priors (resident path): the priors of the loaded batch, in the caller's track order; NULL
+ * clears them.  Call order and lifetime are msckf_set_view_sigma's: after the batch load, before or after
+ * msckf_set_tracks / msckf_set_view_sigma / msckf_run_select / msckf_replan, before the run; the next batch
+ * load and msckf_set_state clear them; propagation, msckf_set_poses and rows updates leave them.  msckf_run,
+ * msckf_run_timed and the retry inside msckf_get_result honour them.  msckf_run_select knows nothing of them:
+ * a skipped track stays skipped, a refreshed point becomes p_lin.  msckf_stats.stacked_rows counts 2M for an
+ * accepted prior track.  The K5 plan of the loaded batch is made afresh (a prior track brings 2M rows, not
+ * 2M - 3).  A prior on a long track that the batch load had split re-sorts the batch with every track in one
+ * block (the route of a long track that cannot be split): MSCKF_ERR_STATE where that would lose what
+ * msckf_set_tracks or msckf_run_select brought for a caller-supplied batch -- set such priors first.
+ * Errors, with nothing changed: MSCKF_ERR_ARG for reserved != 0, unknown flags, a prior whose mean or
+ * covariance has an entry that is not finite, whose covariance is not bitwise symmetric or has no Cholesky
+ * factor with finite pivots > 0, a prior on a track of more than MSCKF_MAX_TRACK_PRIOR views, or an
+ * MSCKF_DTYPE_F32 context; MSCKF_ERR_STATE without a loaded batch or under a group exchange.  While priors
+ * are in force msckf_run_compress and the export / merge calls answer MSCKF_ERR_STATE.
+ * msckf_update_prior: msckf_update_sigma with the priors behind sigma_view (NULL: msckf_update_sigma itself).
+ * msckf_get_prior_distance: waits for the stream; d2[F] (caller's order) of the last run,
+ * (pbar - p_lin)^T Sigma_p^-1 (pbar - p_lin) at the run's linearisation point, 0 for a plain or skipped track.
+ * MSCKF_ERR_STATE when the loaded batch's last run had no priors or its results have been voided since. */
+#define MSCKF_PRIOR_AT_MEAN 1
+#define MSCKF_MAX_TRACK_PRIOR 30    /* 2M + 3 rows on 64 lanes */
+typedef struct msckf_point_priors {
+    const uint8_t* has;     /* F, the caller's track order; 0: a plain track                         */
+    const double*  mean;    /* 3F, world frame; read where has[j]                                    */
+    const double*  cov;     /* 9F, row-major 3x3; read where has[j]                                  */
+    int32_t flags;          /* 0 | MSCKF_PRIOR_AT_MEAN                                               */
+    int32_t reserved;       /* 0                                                                     */
+} msckf_point_priors;
+int msckf_set_point_priors(msckf_ctx* ctx, const msckf_point_priors* priors);
+int msckf_update_prior(msckf_ctx* ctx, int32_t N, const double* P,
+                       const double* cam_R, const double* cam_t,
+                       const double* cam_R0, const double* cam_t0,
+                       const double* gravity, const double* Kinv, double sigma,
+                       int32_t F, const int32_t* view_ptr, const double* obs_uv,
+                       const int32_t* obs_slot, const double* idp_base,
+                       const double* idp_m, const double* idp_rho, const double* sigma_view,
+                       const msckf_point_priors* priors,
+                       const double* chi2_crit, int32_t n_crit,
+                       double* dx, double* P_out, uint8_t* accepted, msckf_stats* stats);
+int msckf_get_prior_distance(msckf_ctx* ctx, double* d2);
+
 /* ---- resident path: the same update split so inputs can stay in HBM ---- */
 /* Upload filter state read by update(): P, clone poses, gravity, K^-1, sigma, chi2 table. */
 int msckf_set_state(msckf_ctx* ctx, int32_t N, const double* P,

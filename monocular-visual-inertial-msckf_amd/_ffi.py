@@ -49,8 +49,16 @@ SYMBOLS = [
     "msckf_update_sigma", "msckf_set_view_sigma",
     "msckf_run_rows", "msckf_run_fix", "msckf_get_rows_gate",
     "msckf_set_robust", "msckf_get_view_weights",
+    "msckf_set_point_priors", "msckf_update_prior", "msckf_get_prior_distance",
 ]
 ROBUST_OFF, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2
+PRIOR_AT_MEAN = 1       # MSCKF_PRIOR_AT_MEAN: linearise a prior track at the prior's mean
+MAX_TRACK_PRIOR = 30    # MSCKF_MAX_TRACK_PRIOR: views of a track whose point carries a prior
+
+
+class PointPriorsC(C.Structure):
+    """msckf_point_priors: which tracks' points carry a prior (caller's track order), its mean and covariance."""
+    _fields_ = [("has", C.c_void_p), ("mean", C.c_void_p), ("cov", C.c_void_p), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RobustParamsC(C.Structure):
@@ -159,6 +167,14 @@ def load():
     lib.msckf_set_robust.restype = C.c_int
     lib.msckf_get_view_weights.argtypes = [vp, _dp, _dp, _ip]
     lib.msckf_get_view_weights.restype = C.c_int
+    lib.msckf_set_point_priors.argtypes = [vp, C.POINTER(PointPriorsC)]
+    lib.msckf_set_point_priors.restype = C.c_int
+    # msckf_update_sigma with the priors (nullable) behind sigma_view
+    lib.msckf_update_prior.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_int32, _ip, _dp,
+                                       _ip, _dp, _dp, _dp, _dp, C.POINTER(PointPriorsC), _dp, C.c_int32, _dp, _dp, _up, C.POINTER(Stats)]
+    lib.msckf_update_prior.restype = C.c_int
+    lib.msckf_get_prior_distance.argtypes = [vp, _dp]
+    lib.msckf_get_prior_distance.restype = C.c_int
     lib.msckf_set_state.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, C.c_int32]
     lib.msckf_set_state.restype = C.c_int
     lib.msckf_set_features.argtypes = [vp, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp]

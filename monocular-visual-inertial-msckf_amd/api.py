@@ -169,6 +169,19 @@ class UpdateEngine:
         st = _ffi.Stats()
         # (per-view noise: sigma_view behind idp_rho, or NULL -- msckf_update is this call with NULL)
         vs = None if prob.view_sigma is None else self._view_sigma(prob.view_sigma, int(a["view_ptr"][-1]))
+        if prob.point_prior is not None:
+            # (priors on the tracks' points behind sigma_view: msckf_update_prior; without them the call below, as ever)
+            pc, keep = self._point_priors(prob.point_prior, F)
+            rc = self._lib.msckf_update_prior(
+                self._h, N, _ffi.dptr(a["P"]), _ffi.dptr(a["cam_R"]), _ffi.dptr(a["cam_t"]), _ffi.dptr(a["cam_R0"]),
+                _ffi.dptr(a["cam_t0"]), _ffi.dptr(a["g"]), _ffi.dptr(a["Kinv"]), float(prob.sigma), F,
+                _ffi.iptr(a["view_ptr"]), _ffi.dptr(a["obs_uv"]), _ffi.iptr(a["obs_slot"]), _ffi.dptr(a["idp_base"]),
+                _ffi.dptr(a["idp_m"]), _ffi.dptr(a["idp_rho"]), None if vs is None else _ffi.dptr(vs), C.byref(pc), _ffi.dptr(chi),
+                int(chi.size), _ffi.dptr(dx), _ffi.dptr(P_out), _ffi.uptr(acc), C.byref(st))
+            del keep
+            self._check(rc)
+            self._N, self._F, self._views = N, F, int(a["view_ptr"][-1])
+            return UpdateResult(rc, dx, P_out, acc[:F].copy(), st.as_dict())
         rc = self._lib.msckf_update_sigma(
             self._h, N, _ffi.dptr(a["P"]), _ffi.dptr(a["cam_R"]), _ffi.dptr(a["cam_t"]), _ffi.dptr(a["cam_R0"]),
             _ffi.dptr(a["cam_t0"]), _ffi.dptr(a["g"]), _ffi.dptr(a["Kinv"]), float(prob.sigma), F,
@@ -227,6 +240,42 @@ class UpdateEngine:
         self.set_features(prob)
         if prob.view_sigma is not None:
             self.set_view_sigma(prob.view_sigma)
+        if prob.point_prior is not None:
+            self.set_point_priors(prob.point_prior)
+
+    @staticmethod
+    def _point_priors(pri, F: int):
+        """(msckf_point_priors, the arrays it points into) of a `synth.PointPriors` for a batch of F tracks."""
+        if pri.F != F:
+            raise ValueError(f"the priors name {pri.F} tracks, the batch holds {F}")
+        has = np.ascontiguousarray(pri.has, dtype=np.uint8)
+        mean, cov = _ffi.f64(pri.mean), _ffi.f64(pri.cov)
+        pc = _ffi.PointPriorsC(_ffi.uptr(has), _ffi.dptr(mean), _ffi.dptr(cov), _ffi.PRIOR_AT_MEAN if pri.at_mean else 0, 0)
+        return pc, (has, mean, cov)
+
+    def set_point_priors(self, pri=None):
+        """Priors on the points of the loaded batch's tracks (`msckf_set_point_priors`; not in the reference): a
+        `synth.PointPriors` in the input order of the tracks -- p_j ~ N(mean[j], cov[j]) in the world frame where
+        `has[j]`, three whitened rows in front of the null-space projection, 2M rows of the track in the update
+        (a track of one view included); `at_mean` linearises a prior track at the mean.  `None` clears.  Call it
+        after the batch load (`set_features`, `load_tracks`, `load_tracks_where`), before the run; the next batch
+        load and `set_state` clear it.  `EngineError` (`ERR_ARG`) for a prior that is not finite, not bitwise
+        symmetric or not positive definite, on a track of more than 30 views, or an f32 engine; (`ERR_STATE`)
+        without a loaded batch or under a group exchange -- the priors in force stay as they were."""
+        if pri is None:
+            self._check(self._lib.msckf_set_point_priors(self._h, None), allow_noop=False)
+            return
+        pc, keep = self._point_priors(pri, self._F if self._F else pri.F)      # (no batch: the engine answers ERR_STATE, reading nothing)
+        self._check(self._lib.msckf_set_point_priors(self._h, C.byref(pc)), allow_noop=False)
+        del keep
+
+    def prior_distance(self) -> np.ndarray:
+        """(pbar - p_lin)^T Sigma_p^-1 (pbar - p_lin) per track of the last run at its linearisation point, 0 for a
+        plain or skipped track (`msckf_get_prior_distance`; waits for the stream).  `EngineError` (`ERR_STATE`) when
+        the loaded batch's last run had no priors or its results were voided since."""
+        d2 = np.zeros(max(self._F, 1))
+        self._check(self._lib.msckf_get_prior_distance(self._h, _ffi.dptr(d2)), allow_noop=False)
+        return d2[:self._F].copy()
 
     @staticmethod
     def _view_sigma(view_sigma, n_views: int) -> np.ndarray:
@@ -1067,7 +1116,7 @@ class UpdateEngine:
         return T, rn
 
     # -- reference-shaped drop-in ---------------------------------------------
-    def update(self, filt, features, view_sigma=None) -> int:
+    def update(self, filt, features, view_sigma=None, point_priors=None) -> int:
         """Drop-in for `MSCKF.update(features)` (reference `MSCKF.py:570-609`)
         including `correct` (`:611-661`).  `filt` is any object with the
         attributes the reference method reads: `state.cameras` (ordered mapping
@@ -1078,13 +1127,17 @@ class UpdateEngine:
         `view_sigma`: optional mapping feature key -> one standard deviation per view, in the order of
         `Feature.keypoints` and in `sigma_image`'s units (R_o = blockdiag(sigma_v^2 I_2) in place of `:589`; a
         feature the mapping does not name stays at `sigma_image`).  `None`: the reference's update.
+        `point_priors`: optional mapping feature key -> (mean (3,), cov (3, 3)) of a known landmark in the world frame
+        (`set_point_priors`); features it does not name are plain tracks.
         A robust loss needs no argument here: `set_robust` is a setting of the engine and this call honours it.
         Returns the status (0 updated / 1 no-op); mutates `filt` like the reference."""
-        from .pack import problem_from_reference, view_sigma_from_reference
+        from .pack import point_priors_from_reference, problem_from_reference, view_sigma_from_reference
         from .inject import inject_state
         prob = problem_from_reference(filt, features)
         if view_sigma is not None:
             prob.view_sigma = view_sigma_from_reference(features, view_sigma, prob.sigma)
+        if point_priors is not None:
+            prob.point_prior = point_priors_from_reference(features, point_priors)
         res = self.update_problem(prob)
         filt.number_of_residuals_discarded_for_gasting_test += res.n_rejected        # MSCKF.py:578
         if res.status != 0:
@@ -1093,18 +1146,20 @@ class UpdateEngine:
         inject_state(filt.state, res.dx)                                              # MSCKF.py:616-661
         return 0
 
-    def process_features(self, filt, view_sigma=None, refine_iters: int = 0) -> int:
+    def process_features(self, filt, view_sigma=None, refine_iters: int = 0, point_priors=None) -> int:
         """Drop-in for `MSCKF.process_features()` (reference `MSCKF.py:450-456`):
         `get_valid_features(self.features)` and `update(valid_features)` in one device pass,
         then `remove_features(lost_features)` through the filter's own method.  Mutates the
         features' inverse-depth points (`:488`) and the filter like the reference does.
-        `view_sigma`: as in `update`, keyed like `filt.features`.
+        `view_sigma`, `point_priors`: as in `update`, keyed like `filt.features`.  The selection knows nothing of priors: a
+        track it skips stays skipped, a refreshed point is where the prior track is linearised.
         `refine_iters`: 0 the reference's linear triangulation; 1..32 refines each triangulated point on the device
         under the current clone poses before the update (`run_select`); the features then carry the refined points.
         A robust loss set with `set_robust` stays in force (no argument here): its weights are formed at the refreshed points.
         Returns 0 updated / 1 no-op."""
         import dataclasses
-        from .pack import problem_from_reference, select_params_from_reference, tracks_from_reference, view_sigma_from_reference
+        from .pack import (point_priors_from_reference, problem_from_reference, select_params_from_reference, tracks_from_reference,
+                           view_sigma_from_reference)
         from .inject import inject_state
         feats = filt.features
         if len(feats) == 0:
@@ -1112,6 +1167,8 @@ class UpdateEngine:
         prob = problem_from_reference(filt, feats)
         if view_sigma is not None:
             prob.view_sigma = view_sigma_from_reference(feats, view_sigma, prob.sigma)
+        if point_priors is not None:
+            prob.point_prior = point_priors_from_reference(feats, point_priors)
         self.load(prob)
         self.set_tracks(tracks_from_reference(feats))
         self.run_select(dataclasses.replace(select_params_from_reference(filt), refine_iters=int(refine_iters)), prob.K)

@@ -27,6 +27,7 @@
 #include "../../include/msckf_mi355x.h"
 #include "k_feature.h"
 #include "k_feature_wide.h"
+#include "k_feature_prior.h"
 #include "k_fold.h"
 #include "k_gain.h"
 #include "k_gstream.h"
@@ -48,6 +49,7 @@
 #include "batch_order.h"
 #include "rows_args.h"
 #include "robust_weight.h"
+#include "point_prior.h"
 
 static_assert(TrackMirror::kOk == MSCKF_OK && TrackMirror::kErrArg == MSCKF_ERR_ARG && TrackMirror::kErrDupSlot == MSCKF_ERR_DUP_SLOT,
               "track_mirror.h returns the ABI's codes");
@@ -290,6 +292,7 @@ struct RunRecord {
     int rows_m = 0;                       // rows: the measurement's row count (msckf_stats.stacked_rows)
     bool injected = false;                // msckf_commit_inject added this run's dx to the nominal state: a run is injected once
     bool robust = false;                  // pipeline: K1 read the robust weights k_robust wrote for it (msckf_get_view_weights)
+    bool prior = false;                   // pipeline: k_feature_prior ran for the batch's prior tracks (msckf_get_prior_distance)
     long serial = 0;                     // finish_run numbers the runs
 };
 
@@ -425,6 +428,21 @@ struct msckf_ctx {
     msckf_robust_params rob_launched{};
     Buf dRob;
     bool rob_k1 = false;
+    // priors on the tracks' points (msckf_set_point_priors; point_prior.h, k_feature_prior.h).  They belong to the batch, like the
+    // weights.  With them in force the plain K1-K4 launches skip the prior tracks by k_prior_prepare's mask and k_feature_prior
+    // takes them by prior_list; the K5 plan counts 2M rows for them (prior_plan_stale: the plan was made for another setting and
+    // is made afresh in front of the next run).  dPrior: W [9F] | mean [3F] | d2 [F] | m' [3F] | rho' [F] | list [F] | has [F] |
+    // mask [F], sorted order
+    bool have_prior = false;
+    int prior_flags = 0;
+    std::vector<unsigned char> prior_has_s;           // [F] sorted order
+    std::vector<int> prior_list;                      // sorted indices of the prior tracks, ascending
+    Buf dPrior;
+    bool prior_plan_stale = false;
+    bool plan_with_flags = false;          // the current plan was made from k_select's flags (msckf_replan)
+    bool force_unsplit = false;            // the batch load in progress splits no track (a prior on a long track: one block)
+    bool prior_unsplit = false;            // the loaded batch was loaded that way (clearing the priors loads it as it was)
+    std::vector<int> store_rows, store_lost, store_tracked;   // what the last msckf_tracks_load* loaded (reload_batch)
     const GatherRec* gather_rec = nullptr; // the batch's records where k_gather read them (pinned host image or the raw arena)
     std::vector<double> chi2_cache;
     bool defer_state_sync = false;        // msckf_update: the feature upload's sync covers the state upload
@@ -851,11 +869,17 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
                      const std::vector<int>& view_sorted, const std::vector<unsigned char>* valid, const std::vector<Run>& runs) {
     const int N = c->N, dc = 6 * N;
     auto live = [&](int i) { return !valid || ((*valid)[i] & 1); };
-    int max_span = 0, mm_live = 0, F = 0;                 // F: entries of the runs (they size the leaves)
+    // rows an entry brings at most: 2M - 3, or 2M for a track whose point carries a prior (msckf_set_point_priors)
+    auto rows_of = [&](int e) {
+        const int M = view_sorted[e + 1] - view_sorted[e];
+        const bool prior = c->have_prior && e < (int)c->prior_has_s.size() && c->prior_has_s[e];
+        return prior ? 2 * M : std::max(2 * M - 3, 1);
+    };
+    int max_span = 0, q_live = 0, F = 0;                  // F: entries of the runs (they size the leaves)
     for (const Run& run : runs) {
         F += run.e - run.b;
         for (int f = run.b; f < run.e; ++f)
-            if (live(f)) { max_span = std::max(max_span, fmax[f] - fmin[f] + 1); mm_live = std::max(mm_live, view_sorted[f + 1] - view_sorted[f]); }
+            if (live(f)) { max_span = std::max(max_span, fmax[f] - fmin[f] + 1); q_live = std::max(q_live, rows_of(f)); }
     }
     if (c->xchg && c->xchg_span > 0) {
         if (max_span > c->xchg_span) return false;                        // the caller's figure does not cover this shard: root blocks
@@ -880,8 +904,8 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
         //  wavefronts of two: 142 against 116 us at 10000 features)
         c->leaf_tall = wide_leaf && tall_mode != 0;
         const int rb = wide_leaf ? (c->leaf_tall ? LSweepGeom<6, LS_RS6T>::RB : LSweepGeom<6, LS_RS6>::RB) : LSweepGeom<4, LS_RS4>::RB;
-        const int mm = std::max(mm_live, 1);                                     // longest track the leaves will see
-        const int fpb = std::max(1, std::min(LS_FB, rb / std::max(2 * mm - 3, 1)));
+        const int qm = std::max(q_live, 1);                                      // most rows of a track the leaves will see
+        const int fpb = std::max(1, std::min(LS_FB, rb / qm));
         c->leaf_nf = (F >= big_batch && !c->leaf_tall) ? 12 : 8;
         const int unit = c->leaf_nf * fpb;
         static const int leaf_target = [] { const char* e = std::getenv("MSCKF_LEAF_TARGET"); return e ? std::max(1, atoi(e)) : 240; }();
@@ -939,7 +963,7 @@ bool build_plan_band(msckf_ctx* c, const std::vector<int>& fmin, const std::vect
             int hi = fmax[f], rows = 0, e = f, last = f, nlive = 0;
             while (e < F && (e - f) < 128 && (!live(e) || fmin[e] == s)) {
                 if (live(e)) {
-                    const int r = std::max(2 * (view_sorted[e + 1] - view_sorted[e]) - 3, 1);
+                    const int r = rows_of(e);
                     if (e > f && (rows + r > leaf_rows || nlive >= leaf_feats)) break;
                     rows += r; ++nlive;
                     hi = std::max(hi, fmax[e]);
@@ -1156,6 +1180,7 @@ void plan_batch(msckf_ctx* c, const std::vector<int>& fmin, const std::vector<in
 }
 
 int upload_plan(msckf_ctx* c);
+int replan_for_priors(msckf_ctx* c);
 
 int launch_fold_levels(msckf_ctx* c, const std::vector<std::pair<int, int>>& levels,
                        const std::vector<FoldNode>& all_nodes, hipStream_t st = nullptr, const FoldNode* dnodes = nullptr) {
@@ -1391,6 +1416,22 @@ inline double* rem_rows(msckf_ctx* c) { return rem_in_record(c) ? ptr<double>(c-
 inline int* drem_count(msckf_ctx* c) { return reinterpret_cast<int*>(ptr<double>(c->dRem) + (size_t)16 * GS_MAX_NB2 * (6 * c->maxN + 1)); }   // behind the matrix
 inline int* rem_count(msckf_ctx* c) { return rem_in_record(c) ? reinterpret_cast<int*>(ptr<double>(c->dRbuf) + rec_rem_off(c)) : drem_count(c); }
 
+// The priors of the loaded batch on the device (msckf_ctx::dPrior), F entries each in the sorted order
+struct PriorImage {
+    double* W; double* mean; double* d2; double* m; double* rho;     // [9F] [3F] [F] [3F] [F]
+    int* list; unsigned char* has; unsigned char* mask;               // [F] each
+};
+inline size_t prior_image_bytes(int F) { return (size_t)F * (72 + 24 + 8 + 24 + 8 + 4 + 1 + 1); }
+inline PriorImage prior_image(msckf_ctx* c) {
+    const size_t F = c->F;
+    char* b = static_cast<char*>(c->dPrior.p);
+    PriorImage im;
+    im.W = reinterpret_cast<double*>(b); im.mean = im.W + 9 * F; im.d2 = im.mean + 3 * F; im.m = im.d2 + F; im.rho = im.m + 3 * F;
+    im.list = reinterpret_cast<int*>(im.rho + F);
+    im.has = reinterpret_cast<unsigned char*>(im.list + F); im.mask = im.has + F;
+    return im;
+}
+
 // msckf_set_robust is on: k_robust in front of K1, on the main stream and in front of the fork to the second stream, so that
 // every K1 of the launch set below (short, split, wide) reads what it wrote.  The weights go to dRob; a.obs_w is pointed at them.
 int launch_robust(msckf_ctx* c, FeatureArgs& a) {
@@ -1436,7 +1477,24 @@ int launch_feature(msckf_ctx* c) {
     a.select = c->use_select ? ptr<unsigned char>(c->dSelFlags) : nullptr;
     a.stamps = c->dStamps.p ? ptr<long long>(c->dStamps) + 8 * 8192 : nullptr;   // behind the fold stamps
     a.zero_idx = c->ord.stack_elems;
+    // priors on the tracks' points: k_prior_prepare writes the byte the plain launches below skip the prior tracks by and, with
+    // MSCKF_PRIOR_AT_MEAN, the run's own m / rho, which every K1 of the run reads (k_robust included); k_feature_prior takes the
+    // prior tracks by their list, behind the plain launches of the main stream (it overwrites the "skipped" verdict they left)
+    const bool pri = c->have_prior && !c->prior_list.empty();
+    PriorImage pim{};
+    if (pri) {
+        pim = prior_image(c);
+        PriorPrepareArgs pp{};
+        pp.F = c->F; pp.has = pim.has; pp.select = a.select; pp.mask = pim.mask;
+        pp.at_mean = (c->prior_flags & MSCKF_PRIOR_AT_MEAN) ? 1 : 0;
+        pp.mean = pim.mean; pp.base = a.idp_base; pp.m_in = a.idp_m; pp.rho_in = a.idp_rho; pp.m_out = pim.m; pp.rho_out = pim.rho;
+        hipLaunchKernelGGL(k_prior_prepare, dim3((c->F + 255) / 256), dim3(256), 0, c->stream, pp);
+        HIPCHK(c, hipGetLastError());
+        if (pp.at_mean) { a.idp_m = pim.m; a.idp_rho = pim.rho; }
+    }
     if (c->robust.loss != MSCKF_ROBUST_OFF) { if (int rcr = launch_robust(c, a)) return rcr; }
+    const unsigned char* const sel_run = a.select;         // the run's own flags (k_select's, or none)
+    if (pri) a.select = pim.mask;
     c->gate_direct =c->want_direct && !c->use_select;      // (long tracks: k_feature<64, true> mirrors its track's results as well)
     if (c->gate_direct) { a.rank_h = static_cast<int*>(c->hGate); a.acc_h = static_cast<unsigned char*>(c->hGate) + (size_t)c->ord.Fs * 4; }
     // one launch per class of tracks: the short tracks [0, Fb) and the long ones [Fb, F), which are split (k_feature<64, true>
@@ -1501,6 +1559,13 @@ int launch_feature(msckf_ctx* c) {
         wa.list = reinterpret_cast<const int*>(static_cast<const char*>(c->dRawArena.p) + c->wide_list_off);
         hipLaunchKernelGGL(k_feature_wide, dim3((unsigned)c->wide_list.size()), dim3(FEATW_T), FEATW_LDS_BYTES, st, wa);
     } else go(0, c->F, c->ord.Mmax);
+    if (pri) {
+        FeaturePriorArgs wp{};
+        a.f0 = 0; a.F = (int)c->prior_list.size(); a.split = nullptr; a.select = sel_run;
+        wp.a = a;
+        wp.list = pim.list; wp.W = pim.W; wp.mean = pim.mean; wp.sigma = c->sigma; wp.d2 = pim.d2;
+        hipLaunchKernelGGL(k_feature_prior, dim3((unsigned)c->prior_list.size()), dim3(FEATP_T), 0, c->stream, wp);
+    }
     HIPCHK(c, hipGetLastError());
     return MSCKF_OK;
 }
@@ -2078,6 +2143,7 @@ int run_rows(msckf_ctx* c, int m, int n_cols, const double* H, const double* rz,
 int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     if (!c->have_state || !c->have_features) return MSCKF_ERR_STATE;
     int rc;
+    if (c->prior_plan_stale && (rc = replan_for_priors(c)) != MSCKF_OK) return rc;
     RunRecord rec;
     rec.kind = RunKind::Pipeline; rec.gain = with_gain;
     if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[0], c->stream));
@@ -2085,6 +2151,7 @@ int run_pipeline(msckf_ctx* c, bool with_gain, hipEvent_t* stage_ev) {
     if (!c->feature_launched && (rc = launch_feature(c)) != MSCKF_OK) return rc;
     c->feature_launched = false;
     rec.robust = c->F > 0 && c->rob_k1;
+    rec.prior = c->F > 0 && c->have_prior;
     if (stage_ev) HIPCHK(c, hipEventRecord(stage_ev[1], c->stream));
     // split long tracks: their remainder blocks' tree follows k_feature<64, true> on the second stream, beside the band
     // pipeline; the leaves below read the narrow blocks that kernel wrote
@@ -2603,6 +2670,7 @@ int msckf_set_state(msckf_ctx* c, int32_t N, const double* P, const double* cam_
     c->have_state = true;
     c->last.ran = false;
     c->have_w = false;                    // w_v = sigma / sigma_v was taken at the sigma that is replaced here
+    if (c->have_prior) { c->have_prior = false; c->prior_list.clear(); c->prior_has_s.clear(); c->prior_plan_stale = true; }   // sigma W likewise
     tracks_clear(c);                      // clone slots lose their meaning
     return MSCKF_OK;
 }
@@ -2641,6 +2709,9 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     c->batch_from_store = false;
     c->no_wide = false;
     c->have_w = false;                    // the weights belonged to the batch that is gone
+    c->have_prior = false; c->prior_list.clear(); c->prior_has_s.clear();      // ... and so did the priors
+    c->prior_plan_stale = false; c->plan_with_flags = false;                   // (the plan below is made without them)
+    c->prior_unsplit = c->force_unsplit;
     c->gather_rec = nullptr;
     c->wide_list.clear(); c->narrow_mmax = 0;
     if (F == 0) {
@@ -2716,7 +2787,7 @@ static int set_features_impl(msckf_ctx* c, int32_t F, const int32_t* view_ptr, c
     // key = (class, first slot, last slot); class 0: tracks of up to WIDE_SPAN clone slots (and long ones that cannot be split:
     // views out of slot order, more than SPLIT_MAXG groups, more views than k_feature<64> holds); class 2: long tracks, split
     // (a batch with a wide track splits none: every track keeps one block, and the batch one plan on the merge tree)
-    const bool split = split_ok(c, N) && !has_wide;
+    const bool split = split_ok(c, N) && !has_wide && !c->force_unsplit;
     std::vector<int> key_in(F);
     std::vector<unsigned char> M_in(F);
     ScanPart tot;
@@ -2993,6 +3064,7 @@ static int replan_current(msckf_ctx* c, bool one_plan) {
     if (one_plan) c->no_wide = true;
     c->plan_valid = false;
     plan_batch(c, c->ord.h_fmin, c->ord.h_fmax, c->ord.h_view, nullptr);
+    c->plan_with_flags = false;
     c->plan_no_wide = true;                // (not a plan the cache may hand to the next batch)
     c->gather_off = c->rbuf_doubles;
     const size_t need = (c->rbuf_doubles + 16) * 8;
@@ -3005,6 +3077,7 @@ static int replan_current(msckf_ctx* c, bool one_plan) {
 int msckf_run_compress(msckf_ctx* c) {
     if (!c) return MSCKF_ERR_ARG;
     if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
+    if (c->have_features && c->have_prior) { c->last_error = "priors on the tracks' points are in force (msckf_set_point_priors): no sharded update"; return MSCKF_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     if (c->have_features && c->wide_active && !c->xchg_planned) {
         // the compressed block leaves this context (msckf_export_block): one plan for every track, the wide ones included
@@ -3379,6 +3452,7 @@ int msckf_replan(msckf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->plan_valid = false;                 // the plan no longer covers every candidate: the next upload plans afresh
     plan_batch(c, c->ord.h_fmin, c->ord.h_fmax, c->ord.h_view, &flags);
+    c->plan_with_flags = true; c->prior_plan_stale = false;       // (made for the priors in force, if any)
     c->gather_off = c->rbuf_doubles;
     // the blocks moved inside the R workspace: entries below their diagonals must read as zero again
     {
@@ -3392,6 +3466,19 @@ int msckf_replan(msckf_ctx* c) {
     c->us_host_prep = (float)(now_us() - t0);
     c->last.ran = false;
     return MSCKF_OK;
+}
+
+// Priors were set or cleared since the plan was made: a prior track brings 2M rows to its leaf, a plain one 2M - 3 (plan_batch
+// reads the setting in force).  The same kind of plan as the one at hand -- from k_select's flags where msckf_replan made it.
+extern "C++" {
+namespace {
+int replan_for_priors(msckf_ctx* c) {
+    c->prior_plan_stale = false;
+    if (c->F == 0) return MSCKF_OK;
+    if (c->plan_with_flags && c->use_select) return msckf_replan(c);
+    return replan_current(c, false);
+}
+}  // namespace
 }
 
 int msckf_debug_time_select(msckf_ctx* c, int32_t iters, float* us_per_launch) {
@@ -3776,7 +3863,157 @@ static int tracks_load_rows(msckf_ctx* c, int F, const std::vector<int>& rows, c
     if (rc != MSCKF_OK) return rc;
     c->have_tracks = true;                // the lines and counters went with the batch (msckf_set_tracks' half)
     c->batch_from_store = F > 0;
+    if (&rows != &c->store_rows) {        // (what reload_batch loads again)
+        c->store_rows = rows;
+        c->store_lost.assign(lost_for, lost_for + F); c->store_tracked.assign(tracked_for, tracked_for + F);
+    }
     return MSCKF_OK;
+}
+
+// ---- priors on the tracks' points (point_prior.h, k_feature_prior.h) ------------------------------------------------
+// The loaded batch once more: the caller's arrays from the pinned image, or the store's rows again; the per-view weights are
+// carried over.  unsplit: every track in one block (a prior track has no split form); else as a load without priors has it.
+static int reload_batch(msckf_ctx* c, bool unsplit) {
+    const int F = c->F, sumM = c->sumM;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream2));
+    c->feat_busy = false;
+    const bool had_w = c->have_w;
+    std::vector<double> w_keep;
+    if (had_w) { const double* hw = reinterpret_cast<const double*>(static_cast<const char*>(c->hFeat) + c->w_raw_off); w_keep.assign(hw, hw + sumM); }
+    const std::vector<int> vp = c->h_view_in;
+    int rc;
+    c->force_unsplit = unsplit;
+    if (c->batch_from_store) {
+        const std::vector<int> rows = c->store_rows, lost = c->store_lost, tracked = c->store_tracked;
+        rc = tracks_load_rows(c, F, rows, vp, lost.data(), tracked.data());
+    } else {
+        const RawLayout raw = raw_layout(F, sumM);
+        const char* hb = static_cast<const char*>(c->hFeat);
+        auto arr = [&](size_t off, size_t n) { const double* p = reinterpret_cast<const double*>(hb + off); return std::vector<double>(p, p + n); };
+        const std::vector<double> uv = arr(raw.r_uv, (size_t)sumM * 2), base = arr(raw.r_base, (size_t)F * 3), m = arr(raw.r_m, (size_t)F * 3),
+                                  rho = arr(raw.r_rho, (size_t)F);
+        const int32_t* sp = reinterpret_cast<const int32_t*>(hb + raw.r_slot);
+        const std::vector<int32_t> slot(sp, sp + sumM);
+        rc = set_features_impl(c, F, vp.data(), uv.data(), slot.data(), base.data(), m.data(), rho.data(), nullptr);
+    }
+    c->force_unsplit = false;
+    if (rc != MSCKF_OK) return rc;
+    if (had_w) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::memcpy(static_cast<char*>(c->hFeat) + c->w_raw_off, w_keep.data(), (size_t)sumM * 8);
+        if (int rcw = launch_gather_w(c)) return rcw;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->have_w = true;
+    }
+    return MSCKF_OK;
+}
+
+int msckf_set_point_priors(msckf_ctx* c, const msckf_point_priors* pr) {
+    if (!c) return MSCKF_ERR_ARG;
+    if (!c->have_state || !c->have_features) return MSCKF_ERR_STATE;
+    const int F = c->F;
+    bool any = false;
+    if (pr) {
+        if (pr->reserved != 0 || (pr->flags & ~MSCKF_PRIOR_AT_MEAN)) return MSCKF_ERR_ARG;
+        if (F > 0 && !pr->has) return MSCKF_ERR_ARG;
+        for (int f = 0; f < F; ++f) any |= pr->has[f] != 0;
+    }
+    if (!any) {                            // NULL, or no track named: no priors in force
+        if (c->have_prior) { c->have_prior = false; c->prior_list.clear(); c->prior_has_s.clear(); c->prior_plan_stale = true; c->last.ran = false; }
+        // (a batch that a prior on a long track had loaded unsplit: as the load without priors has it, where nothing is lost by it)
+        if (c->prior_unsplit && F > 0 && !c->use_select && (!c->have_tracks || c->batch_from_store)) {
+            HIPCHK(c, hipSetDevice(c->device));
+            return reload_batch(c, false);
+        }
+        return MSCKF_OK;
+    }
+    if (c->cfg.dtype == MSCKF_DTYPE_F32 || !pr->mean || !pr->cov) return MSCKF_ERR_ARG;
+    if (c->xchg) { c->last_error = "priors on the tracks' points take no part in a sharded update"; return MSCKF_ERR_STATE; }
+    if (!c->ord.valid || (int)c->h_view_in.size() != F + 1) return MSCKF_ERR_STATE;
+    static_assert(MSCKF_PRIOR_AT_MEAN == kPriorAtMean && MSCKF_MAX_TRACK_PRIOR == kMaxTrackPrior, "point_prior.h and the ABI name one rule");
+    std::vector<double> W((size_t)9 * F, 0.0);             // caller's order
+    for (int f = 0; f < F; ++f) {
+        if (!pr->has[f]) continue;
+        if (c->h_view_in[f + 1] - c->h_view_in[f] > MSCKF_MAX_TRACK_PRIOR) return MSCKF_ERR_ARG;
+        if (!point_prior_ok(pr->mean + 3 * (size_t)f, pr->cov + 9 * (size_t)f)) return MSCKF_ERR_ARG;
+        if (!point_prior_whiten(pr->cov + 9 * (size_t)f, W.data() + 9 * (size_t)f)) return MSCKF_ERR_ARG;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // a prior on a long track the load has split: the batch once more, every track in one block
+    if (c->ord.split_on) {
+        bool on_split = false;
+        for (int s = c->ord.Fb; s < F; ++s) on_split |= pr->has[c->ord.perm[s]] != 0;
+        if (on_split) {
+            if (c->use_select || (c->have_tracks && !c->batch_from_store)) {
+                c->last_error = "a prior on a long track that the batch load split: set it before msckf_set_tracks / msckf_run_select";
+                return MSCKF_ERR_STATE;
+            }
+            if (int rcl = reload_batch(c, true)) return rcl;
+        }
+    }
+    // a run nobody waited for may be reading the image
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream2));
+    if (int rce = ensure(c, c->dPrior, prior_image_bytes(F))) return rce;
+    std::vector<char> img(prior_image_bytes(F), 0);
+    double* hW = reinterpret_cast<double*>(img.data());
+    double* hmean = hW + (size_t)9 * F;
+    int* hlist = reinterpret_cast<int*>(hmean + (size_t)3 * F + F + 3 * F + F);
+    unsigned char* hhas = reinterpret_cast<unsigned char*>(hlist + F);
+    c->prior_has_s.assign(F, 0);
+    c->prior_list.clear();
+    for (int s = 0; s < F; ++s) {                          // sorted position s holds the caller's track perm[s]
+        const int f = c->ord.perm[s];
+        if (!pr->has[f]) continue;
+        std::memcpy(hW + 9 * (size_t)s, W.data() + 9 * (size_t)f, 72);
+        std::memcpy(hmean + 3 * (size_t)s, pr->mean + 3 * (size_t)f, 24);
+        hhas[s] = 1; c->prior_has_s[s] = 1;
+        hlist[c->prior_list.size()] = s; c->prior_list.push_back(s);
+    }
+    HIPCHK(c, hipMemcpyAsync(c->dPrior.p, img.data(), img.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->have_prior = true;
+    c->prior_flags = pr->flags;
+    c->prior_plan_stale = true;            // (2M rows a prior track: the plan is made afresh in front of the run)
+    c->last.ran = false;
+    return MSCKF_OK;
+}
+
+int msckf_get_prior_distance(msckf_ctx* c, double* d2) {
+    if (!c || !d2) return MSCKF_ERR_ARG;
+    // the loaded batch's last run, with priors in force, its results not voided since (RunRecord::ran)
+    if (!c->have_state || !c->have_features || !c->ord.valid || !c->last.ran || !c->last.prior || !c->have_prior) return MSCKF_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int F = c->F;
+    std::vector<double> sorted(F);
+    HIPCHK(c, hipMemcpy(sorted.data(), prior_image(c).d2, (size_t)F * 8, hipMemcpyDeviceToHost));
+    for (int s = 0; s < F; ++s) d2[c->ord.perm[s]] = c->prior_has_s[s] ? sorted[s] : 0.0;
+    return MSCKF_OK;
+}
+
+int msckf_update_prior(msckf_ctx* c, int32_t N, const double* P, const double* cam_R, const double* cam_t,
+                       const double* cam_R0, const double* cam_t0, const double* gravity, const double* Kinv,
+                       double sigma, int32_t F, const int32_t* view_ptr, const double* obs_uv, const int32_t* obs_slot,
+                       const double* idp_base, const double* idp_m, const double* idp_rho, const double* sigma_view,
+                       const msckf_point_priors* priors, const double* chi2_crit, int32_t n_crit, double* dx, double* P_out,
+                       uint8_t* accepted, msckf_stats* stats) {
+    bool any = false;
+    if (priors && priors->has && priors->reserved == 0 && !(priors->flags & ~MSCKF_PRIOR_AT_MEAN))
+        for (int f = 0; f < F; ++f) any |= priors->has[f] != 0;
+    else any = priors != nullptr;                     // (msckf_set_point_priors refuses it below)
+    if (!any || F <= 0)                               // no track named: the one-shot call as it stands
+        return msckf_update_sigma(c, N, P, cam_R, cam_t, cam_R0, cam_t0, gravity, Kinv, sigma, F, view_ptr, obs_uv, obs_slot, idp_base,
+                                  idp_m, idp_rho, sigma_view, chi2_crit, n_crit, dx, P_out, accepted, stats);
+    if (!c) return MSCKF_ERR_ARG;
+    // the resident calls one after the other: K1-K4 cannot start before the priors are known
+    int rc = msckf_set_state(c, N, P, cam_R, cam_t, cam_R0, cam_t0, gravity, Kinv, sigma, chi2_crit, n_crit);
+    if (rc != MSCKF_OK) return rc;
+    if ((rc = set_features_impl(c, F, view_ptr, obs_uv, obs_slot, idp_base, idp_m, idp_rho, nullptr, sigma_view)) != MSCKF_OK) return rc;
+    if ((rc = msckf_set_point_priors(c, priors)) != MSCKF_OK) return rc;
+    if ((rc = msckf_run(c)) != MSCKF_OK) return rc;
+    return msckf_get_result(c, dx, P_out, accepted, stats);
 }
 
 int msckf_tracks_reset(msckf_ctx* c) {
@@ -4298,6 +4535,7 @@ size_t msckf_block_doubles(const msckf_ctx* c) { return c ? (size_t)c->dc * (c->
 int msckf_export_block(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accepted) {
     if (!c || !dst) return MSCKF_ERR_ARG;
     if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
+    if (c->have_features && c->have_prior) { c->last_error = "priors on the tracks' points are in force (msckf_set_point_priors): no sharded update"; return MSCKF_ERR_STATE; }
     if (!c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = msckf_block_doubles(c) * 8;
@@ -4347,6 +4585,7 @@ int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int
                          int32_t total_accepted) {
     if (!c || !blocks || n_blocks < 1) return MSCKF_ERR_ARG;
     if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
+    if (c->have_features && c->have_prior) { c->last_error = "priors on the tracks' points are in force (msckf_set_point_priors): no sharded update"; return MSCKF_ERR_STATE; }
     if (!c->have_state) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const int dc = c->dc;
@@ -4403,6 +4642,7 @@ int msckf_run_merge_gain(msckf_ctx* c, const void* blocks, int32_t n_blocks, int
 int msckf_set_group_exchange(msckf_ctx* c, int on) {
     if (!c) return MSCKF_ERR_ARG;
     if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
+    if (c->have_features && c->have_prior) { c->last_error = "priors on the tracks' points are in force (msckf_set_point_priors): no sharded update"; return MSCKF_ERR_STATE; }
     c->xchg = on != 0;
     c->have_features = false;             // the next msckf_set_features plans with the new layout
     c->plan_valid = false;
@@ -4508,6 +4748,7 @@ int msckf_exchange_split_rule(const msckf_ctx* c, int32_t N, int32_t F, const in
 int msckf_export_groups(msckf_ctx* c, void* dst, int device_ptr, int32_t* n_accepted) {
     if (!c || !dst) return MSCKF_ERR_ARG;
     if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
+    if (c->have_features && c->have_prior) { c->last_error = "priors on the tracks' points are in force (msckf_set_point_priors): no sharded update"; return MSCKF_ERR_STATE; }
     if (!c->last.ran) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = msckf_group_record_doubles(c) * 8;
@@ -4561,6 +4802,7 @@ int collect_masks(msckf_ctx* c, const double* recs, long long rec_stride, int n_
 int run_merge_groups(msckf_ctx* c, const void* records, int32_t n_rec, int device_ptr, int32_t total_accepted, const uint8_t* flags) {
     if (!c || !records || n_rec < 1) return MSCKF_ERR_ARG;
     if (c->have_features && !c->wide_list.empty()) { c->last_error = "the loaded batch holds a track of more than MSCKF_MAX_TRACK views: no sharded update"; return MSCKF_ERR_STATE; }
+    if (c->have_features && c->have_prior) { c->last_error = "priors on the tracks' points are in force (msckf_set_point_priors): no sharded update"; return MSCKF_ERR_STATE; }
     if (!c->have_state) return MSCKF_ERR_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->N, dc = c->dc;

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .synth import SelectParams, TrackTable, UpdateProblem
+from .synth import PointPriors, SelectParams, TrackTable, UpdateProblem
 
 
 def problem_from_reference(filt, features) -> UpdateProblem:
@@ -62,6 +62,33 @@ def view_sigma_from_reference(features, view_sigma, sigma: float) -> np.ndarray:
             sv = np.full(M, float(sigma))
         out.append(sv)
     return np.concatenate(out) if out else np.zeros(0)
+
+
+def idp_from_point(point, base):
+    """(m, rho) with base + m / rho == point, for a caller who builds batches by hand (a map landmark seen from `base`):
+    rho = 1 / |point - base|, m the unit bearing -- the substitution `PointPriors.at_mean` makes on the device
+    (csrc/point_prior.h)."""
+    d = np.asarray(point, dtype=np.float64).reshape(3) - np.asarray(base, dtype=np.float64).reshape(3)
+    n = float(np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]))
+    if not np.isfinite(n) or n == 0.0:
+        raise ValueError("the point lies on the base, or is not finite")
+    rho = 1.0 / n
+    return d * rho, rho
+
+
+def point_priors_from_reference(features, point_priors, at_mean: bool = False) -> PointPriors:
+    """`PointPriors` in the order `problem_from_reference` lays the tracks down: `point_priors` maps a feature key to
+    (mean (3,), cov (3, 3)); a feature it does not name is a plain track."""
+    F = len(features)
+    has, mean, cov = np.zeros(F, dtype=np.uint8), np.zeros((F, 3)), np.zeros((F, 3, 3))
+    unknown = set(point_priors) - set(features)
+    if unknown:
+        raise ValueError(f"point_priors names features the batch does not hold: {sorted(unknown, key=repr)!r}")
+    for j, key in enumerate(features):                 # dict order, MSCKF.py:573
+        if key in point_priors:
+            mu, S = point_priors[key]
+            has[j], mean[j], cov[j] = 1, np.asarray(mu, dtype=np.float64).reshape(3), np.asarray(S, dtype=np.float64).reshape(3, 3)
+    return PointPriors(has, mean, cov, at_mean)
 
 
 def tracks_from_reference(features) -> TrackTable:

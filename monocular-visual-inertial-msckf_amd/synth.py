@@ -27,6 +27,37 @@ WIDTH, HEIGHT = 640, 480
 
 
 @dataclass
+class PointPriors:
+    """What is already known about the points of a batch's tracks: p_j ~ N(mean[j], cov[j]) in the world frame where
+    `has[j]`; a track with `has[j] == 0` is a plain track of an unknown point and its mean / cov are not read.  Not in the
+    reference (its tracks are all of unknown points, `MSCKF.py:554-559`); the rule is csrc/point_prior.h.
+    `at_mean`: linearise a prior track at the prior's mean instead of its own triangulated point."""
+
+    has: np.ndarray          # (F,) uint8
+    mean: np.ndarray         # (F, 3)
+    cov: np.ndarray          # (F, 3, 3), symmetric positive definite where has
+    at_mean: bool = False
+
+    def __post_init__(self):
+        self.has = np.ascontiguousarray(np.asarray(self.has).reshape(-1) != 0, dtype=np.uint8)
+        F = self.has.shape[0]
+        self.mean = np.ascontiguousarray(self.mean, dtype=np.float64).reshape(F, 3)
+        self.cov = np.ascontiguousarray(self.cov, dtype=np.float64).reshape(F, 3, 3)
+        self.at_mean = bool(self.at_mean)
+
+    @property
+    def F(self) -> int:
+        return int(self.has.shape[0])
+
+    def take(self, idx) -> "PointPriors":
+        idx = np.asarray(idx, dtype=np.int64)
+        return PointPriors(self.has[idx], self.mean[idx], self.cov[idx], self.at_mean)
+
+    def subset(self, lo: int, hi: int) -> "PointPriors":
+        return PointPriors(self.has[lo:hi], self.mean[lo:hi], self.cov[lo:hi], self.at_mean)
+
+
+@dataclass
 class UpdateProblem:
     """Flat description of one `MSCKF.update(features)` call (reference
     `src/msckf/MSCKF.py:570`), i.e. everything that call reads."""
@@ -49,6 +80,8 @@ class UpdateProblem:
     # optional (sum M,) standard deviation of each view, in sigma's units: R_o = blockdiag(sigma_v^2 I_2) in place of the
     # reference's sigma^2 I (MSCKF.py:589, :562).  None: every view at sigma
     view_sigma: Optional[np.ndarray] = None
+    # optional priors on the tracks' points (PointPriors, one entry per track).  None: every track of an unknown point
+    point_prior: Optional["PointPriors"] = None
 
     @property
     def N(self) -> int:
@@ -77,7 +110,8 @@ class UpdateProblem:
             obs_uv=self.obs_uv[rows].reshape(-1, 2), obs_slot=self.obs_slot[rows].astype(np.int32),
             idp_base=self.idp_base[idx].reshape(-1, 3), idp_m=self.idp_m[idx].reshape(-1, 3),
             idp_rho=self.idp_rho[idx], meta=dict(self.meta, take=idx),
-            view_sigma=None if self.view_sigma is None else np.asarray(self.view_sigma, dtype=np.float64).reshape(-1)[rows])
+            view_sigma=None if self.view_sigma is None else np.asarray(self.view_sigma, dtype=np.float64).reshape(-1)[rows],
+            point_prior=None if self.point_prior is None else self.point_prior.take(idx))
 
     def subset(self, lo: int, hi: int) -> "UpdateProblem":
         """Contiguous feature shard [lo, hi) with the shared state (P, poses) kept."""
@@ -89,7 +123,8 @@ class UpdateProblem:
             obs_uv=self.obs_uv[a:b], obs_slot=self.obs_slot[a:b],
             idp_base=self.idp_base[lo:hi], idp_m=self.idp_m[lo:hi], idp_rho=self.idp_rho[lo:hi],
             meta=dict(self.meta, shard=(lo, hi)),
-            view_sigma=None if self.view_sigma is None else np.asarray(self.view_sigma, dtype=np.float64).reshape(-1)[a:b])
+            view_sigma=None if self.view_sigma is None else np.asarray(self.view_sigma, dtype=np.float64).reshape(-1)[a:b],
+            point_prior=None if self.point_prior is None else self.point_prior.subset(lo, hi))
 
 
 @dataclass
@@ -271,7 +306,12 @@ def concat_problems(a: UpdateProblem, b: UpdateProblem) -> UpdateProblem:
     if a.view_sigma is not None or b.view_sigma is not None:       # (a side without weights: its views at its sigma)
         side = lambda p: np.full(int(p.view_ptr[-1]), float(p.sigma)) if p.view_sigma is None else np.asarray(p.view_sigma, dtype=np.float64).reshape(-1)
         vs = cat(side(a), side(b))
-    return UpdateProblem(**{**a.__dict__, "view_sigma": vs, "view_ptr": vp, "obs_uv": cat(a.obs_uv, b.obs_uv), "obs_slot": cat(a.obs_slot, b.obs_slot),
+    pp = None
+    if a.point_prior is not None or b.point_prior is not None:     # (a side without priors: plain tracks)
+        side = lambda p: PointPriors(np.zeros(p.F, dtype=np.uint8), np.zeros((p.F, 3)), np.zeros((p.F, 3, 3))) if p.point_prior is None else p.point_prior
+        pa, pb = side(a), side(b)
+        pp = PointPriors(cat(pa.has, pb.has), cat(pa.mean, pb.mean), cat(pa.cov, pb.cov), pa.at_mean or pb.at_mean)
+    return UpdateProblem(**{**a.__dict__, "point_prior": pp, "view_sigma": vs, "view_ptr": vp, "obs_uv": cat(a.obs_uv, b.obs_uv), "obs_slot": cat(a.obs_slot, b.obs_slot),
                             "idp_base": cat(a.idp_base, b.idp_base), "idp_m": cat(a.idp_m, b.idp_m), "idp_rho": cat(a.idp_rho, b.idp_rho)})
 
 
